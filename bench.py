@@ -16,7 +16,12 @@ runs BASELINE configs[3]: D=256 planes split across ranks, each rank's fused ker
 D-slab, and each sample's slab goes point to point (RCCL send/recv over xGMI,
 mvs_amd/depth_shards.py) to the rank that owns the sample, which runs the regulariser.
 
-Also reported (one JSON line, rank 0):
+A plain run sets up, warms up, times --steps steps and prints one JSON line (rank 0): value, ms_per_step,
+the workload, and the warp kernel's GB/s from the HIP events around its launches inside the timed steps.
+--dump-outputs DIR also writes the last timed step's depth maps (DIR/initial_depth.npy, refined_depth.npy,
+float32); inputs and weights are seeded, so two builds can be compared output for output.
+
+With --full the same line also carries (each from runs of its own, after the timed steps):
   roofline        the fp32 step's dominant kernel, conv_0_0 (conv3d_k3_narrow_kernel<8>, fp32 VALU with a
                   depth-Winograd transform): its useful convolution flops per launch / its average launch
                   time (HIP events on its stream inside the timed steps) vs the fp32 peak (157.3 TF, the
@@ -41,17 +46,19 @@ import threading
 import time
 
 REPO = os.path.dirname(os.path.abspath(__file__))
+for sub in ("deep-multiview-depth-estimation_amd", os.path.join("tests", "golden")):
+    sys.path.insert(0, os.path.join(REPO, sub))
+
 # MIOpen find results for the regulariser's convolutions ship with the repo (a text database of
-# chosen solvers, tools/miopen_db), so a fresh box skips most of the multi-minute search.  Must be
-# set before torch initialises MIOpen.
-os.environ.setdefault("MIOPEN_USER_DB_PATH", os.path.join(REPO, "tools", "miopen_db"))
+# chosen solvers, tools/miopen_db), so a fresh box skips most of the multi-minute search.  MIOpen
+# rewrites its database files, so it gets a working copy of them (a temporary directory).  Must be set
+# before torch initialises MIOpen.
+import miopen_db  # noqa: E402
+miopen_db.use()
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
-
-for sub in ("deep-multiview-depth-estimation_amd", os.path.join("tests", "golden")):
-    sys.path.insert(0, os.path.join(REPO, sub))
 
 from cameras import camera_batch, depth_range  # noqa: E402
 from weights import deterministic_state_dict  # noqa: E402
@@ -59,6 +66,7 @@ from weights import deterministic_state_dict  # noqa: E402
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: 8.0 TB/s spec
 MFMA_F16_PEAK_TFS = 2500.0   # MI355X_MICROARCH.md: BF16/F16 ~2.5 PF dense
 MFMA_F32_PEAK_TFS = 157.3    # f32-input MFMA = f32 vector peak
+MAX_STEPS_IN_FLIGHT = 4   # timed_steps: how far the host may run ahead of the GPU
 _T0 = time.perf_counter()
 
 
@@ -90,6 +98,12 @@ def parse():
     ap.add_argument("--planes", type=int, default=None)
     ap.add_argument("--height", type=int, default=512)
     ap.add_argument("--width", type=int, default=640)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything else the docstring lists (other "
+                         "arithmetics and modes, isolated kernels, other configs, train step, CPU baseline); "
+                         "--kernel-iters and the options after it only shape that part")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) as DIR/<name>.npy, float32")
     ap.add_argument("--kernel-iters", type=int, default=20)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-planes", type=int, default=None, help="planes for the CPU sample")
@@ -102,7 +116,14 @@ def parse():
                     help="create the RCCL process group even at world size 1 (exercises the nccl code path)")
     ap.add_argument("--conv-search", choices=("on", "off"), default="off",
                     help="torch.backends.cudnn.benchmark (MIOpen find) for the regulariser convs")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.kernel_only:   # nothing but the isolated-kernel fields, which live behind --full
+        if args.dump_outputs:
+            ap.error("--dump-outputs needs the end-to-end step (drop --kernel-only)")
+        args.full = True
+    return args
 
 
 def init_dist(args):
@@ -137,12 +158,21 @@ def max_over_ranks(x, world, device):
 
 def timed_steps(step, steps, world, device, hooked=False):
     """``steps`` steps bracketed by a barrier + device synchronisation on both sides: (seconds, {kernel kind:
-    average ms}) -- with ``hooked``, HIP events around the step's own kernels (ops.KERNEL_EVENT_HOOK: the
-    warp kernel "cost_volume", the fp32 "conv_0_0", the split head "split_head"), recorded on the stream
-    each is launched on."""
+    average ms}, what the last step returned) -- with ``hooked``, HIP events around the step's own kernels
+    (ops.KERNEL_EVENT_HOOK: the warp kernel "cost_volume", the fp32 "conv_0_0", the split head
+    "split_head"), recorded on the stream each is launched on.
+
+    The host enqueues a step in about 1 ms and the GPU runs it in 5.8.  Left alone the host runs hundreds of
+    steps ahead, each holding its buffers until the GPU reaches it: 192 GB reserved after 300 steps, against
+    11 GB here.  Giving that much memory back (empty_cache, or the process's exit) slowed whatever used the GPU
+    next: 19 to 24 ms per step measured in the following run of this benchmark, 8 ms in the one after.  So the
+    host waits for step i - MAX_STEPS_IN_FLIGHT to finish before it enqueues step i.  The GPU always has queued
+    work (5.8 ms per step with 2, 4 or 8 steps in flight, and at 20, 200 and 1000 steps)."""
     from mvs_amd import ops as mvs_ops
     events = []
+    last = None
     stream = torch.cuda.current_stream(device)
+    in_flight = [torch.cuda.Event() for _ in range(MAX_STEPS_IN_FLIGHT)]
 
     def hook(kind):
         pair = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
@@ -155,8 +185,11 @@ def timed_steps(step, steps, world, device, hooked=False):
         mvs_ops.KERNEL_EVENT_HOOK = hook if hooked else None
         try:
             t0 = time.perf_counter()
-            for _ in range(steps):
-                step()
+            for i in range(steps):
+                if i >= MAX_STEPS_IN_FLIGHT:
+                    in_flight[i % MAX_STEPS_IN_FLIGHT].synchronize()
+                last = step()
+                in_flight[i % MAX_STEPS_IN_FLIGHT].record(stream)
             barrier(world)
             dt = time.perf_counter() - t0
         finally:
@@ -165,7 +198,15 @@ def timed_steps(step, steps, world, device, hooked=False):
     for kind in sorted(set(k for k, _ in events)):
         ev = [p for k, p in events if k == kind]
         kms[kind] = sum(a.elapsed_time(b) for a, b in ev) / len(ev)
-    return dt, kms
+    return dt, kms, last
+
+
+def dump_outputs(path, last):
+    """--dump-outputs: the (initial, refined) depth maps [B, 1, h, w] the last timed step returned, as
+    path/initial_depth.npy and path/refined_depth.npy (float32; 0.3 MB each at the default workload)."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in zip(("initial_depth", "refined_depth"), last):
+        np.save(os.path.join(path, name + ".npy"), t.detach().to("cpu", torch.float32).numpy())
 
 
 DSHARD_PHASES = ("encoder", "shard_kernel", "exchange", "owner_compute", "gather")
@@ -235,6 +276,11 @@ def build_model(D, H, W, device, cv_dtype="float32", arithmetic="fp32"):
     net = MVSNet(MVSConfig(d_num=D, in_h=H, in_w=W, cv_dtype=cv_dtype, arithmetic=arithmetic))
     net.load_state_dict(deterministic_state_dict(net.state_dict()))
     return net.to(device).eval()
+
+
+def warp_alg_bytes(B, V, C, h, w, d_count, cv_elem_bytes=4.0):
+    """Algorithmic HBM bytes of one fused warp + variance launch: fp32 features read once, cost volume written once."""
+    return 4.0 * B * V * C * h * w + cv_elem_bytes * B * C * d_count * h * w
 
 
 def time_kernel(B, V, C, h, w, D, device, iters, d_begin=0, d_count=None, bf16=False, quads=False, store="ncdhw"):
@@ -308,8 +354,7 @@ def time_kernel(B, V, C, h, w, D, device, iters, d_begin=0, d_count=None, bf16=F
     torch.cuda.synchronize()
     main_ms = None if (bf16 and not quads) else sum(e0.elapsed_time(e1) for e0, e1 in ev) / iters
     op_ms = op0.elapsed_time(op1) / iters
-    alg_bytes = 4.0 * B * V * C * h * w + (2.0 if bf16 else 4.0) * B * C * d_count * h * w
-    return main_ms, op_ms, alg_bytes
+    return main_ms, op_ms, warp_alg_bytes(B, V, C, h, w, d_count, 2.0 if bf16 else 4.0)
 
 
 def time_backward(B, V, C, h, w, D, device, iters=5):
@@ -409,12 +454,7 @@ def bf16_step(net32, inputs, B, V, D, H, W, device, world, steps):
         ini32 = net32(*inputs, B, V)[0]
         for _ in range(2):
             ini16 = net(*inputs, B, V)[0]
-        barrier(world)
-        t0 = time.perf_counter()
-        for _ in range(steps):
-            net(*inputs, B, V)
-        barrier(world)
-        dt = time.perf_counter() - t0
+    dt = timed_steps(lambda: net(*inputs, B, V), steps, world, device)[0]
     rel = ((ini16 - ini32).abs() / ini32.abs()).flatten()
     out = {"ms_per_step": 1000.0 * dt / steps, "value": B * world * steps / dt, "steps": steps,
            "initial_depth_rel_diff_vs_fp32": {"median": rel.median().item(), "p99": rel.quantile(0.99).item()
@@ -659,6 +699,40 @@ def cpu_baseline(V, H, W, D):
             "host": info, "calibration": "profiles/cpu_calibration_r02.json"}
 
 
+def headline(args, world, B, V, D, H, W, value, ms_step):
+    """The result line's fields of the timed steps themselves (every run; --full adds the rest)."""
+    return {
+        "metric": "depth maps/sec + warp-kernel HBM GB/s, 3-view 640x512 D=192, 1/2/4/8 GPU",
+        "value": value,
+        "unit": "depth maps/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_step,
+        "higher_is_better": True,
+        "scaling": "weak" if args.mode == "samples" else "strong",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "full": bool(args.full),
+        "data": "synthetic N(0,1) images resident in HBM, real DTU scan-1 cameras, random-init "
+                "weights; BN eval mode, live-region regulariser (train-mode BN as in test.py:61: "
+                "field train_bn of a --full run)",
+        "config": {"workload": "cfg%d: %d-view %dx%d D=%d batch=%d per %s, BN eval, live-region "
+                               "regulariser, fp32 arithmetic" % (
+                       2 if args.mode == "samples" else 4, V, W, H, D, B,
+                       "GPU" if args.mode == "samples" else "job (D sharded)"),
+                   "global_batch": B * (world if args.mode == "samples" else 1),
+                   "views": V, "planes": D, "image_hw": [H, W], "feature_hw": [H // 4, W // 4],
+                   "parallelism": ("samples%d" % world) if args.mode == "samples" else ("dshard%d" % world)},
+        "arithmetic": ("exact fp32 in every layer of the timed step (MVSConfig(arithmetic='fp32'), the default): "
+                       "fp32 cost volume (the reference's torch-CPU law, bit for bit given the sampling matrices), "
+                       "2-D convolutions on fp32 VALU kernels, conv_0_0 / conv_out on fp32 VALU kernels (conv_0_0 "
+                       "with a depth-Winograd F(2,3) transform), every region convolution on the f32-input matrix "
+                       "cores (v_mfma_f32_16x16x4_f32: each product and sum rounded as an fmaf chain), fp32 "
+                       "softmax / soft-argmin / refinement"),
+    }
+
+
 def main():
     threading.Thread(target=_heartbeat, daemon=True).start()
     args = parse()
@@ -693,10 +767,13 @@ def main():
                 step()
                 torch.cuda.synchronize()
                 log("warmup step %d/%d done" % (i + 1, args.warmup))
-        dt, result["step_kernel_ms"] = timed_steps(step, args.steps, world, device,
-                                                   hooked=args.mode == "samples")
+        dt, result["step_kernel_ms"], last = timed_steps(step, args.steps, world, device,
+                                                         hooked=args.mode == "samples")
         log("timed %d steps: %.2f ms/step" % (args.steps, 1000.0 * dt / args.steps))
-        if args.mode == "dshard":
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, last)
+        del last
+        if args.mode == "dshard" and args.full:
             # the same step phase by phase, per rank (not part of the timed region above)
             result["dshard_phases"] = dshard_phase_ms(sharded, step, max(1, min(args.steps, 5)), device, world)
             log("dshard phases (ms, this rank): %s" % dict(zip(DSHARD_PHASES, result["dshard_phases"][rank])))
@@ -704,6 +781,24 @@ def main():
         ms_step = 1000.0 * dt / args.steps
         maps_per_step = B * world if args.mode == "samples" else B
         result["value"] = maps_per_step * args.steps / dt
+        if not args.full:
+            # a plain run ends here: the headline, plus what the timed steps' own events give for free
+            if rank == 0:
+                out = headline(args, world, B, V, D, H, W, result["value"], ms_step)
+                step_k = result["step_kernel_ms"]
+                out["step_kernel_ms"] = step_k
+                if world == 1 and "cost_volume" in step_k:
+                    alg = warp_alg_bytes(B, V, C, h, w, D)
+                    gbs = alg / (step_k["cost_volume"] * 1e-3) / 1e9
+                    out["warp_kernel"] = {"bound": "hbm", "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                          "frac": gbs / HBM_PEAK_GBS, "kernel_ms": step_k["cost_volume"],
+                                          "alg_bytes_per_launch": alg,
+                                          "timing": "HIP events around each launch inside the %d timed steps"
+                                                    % args.steps}
+                print(json.dumps(out), flush=True)
+            if dist.is_initialized():
+                dist.destroy_process_group()
+            return
         if args.mode == "samples":
             # the opt-in split-fp16 arithmetic (MVSConfig(arithmetic="split_f16"): the f16 matrix cores with
             # split operands, the split cost volume, the split head; narrower than fp32)
@@ -713,7 +808,7 @@ def main():
                 for _ in range(2):
                     step()
                 torch.cuda.synchronize()
-            dts, kms = timed_steps(step, args.steps, world, device, hooked=True)
+            dts, kms, _ = timed_steps(step, args.steps, world, device, hooked=True)
             net.set_arithmetic("fp32")
             dts = max_over_ranks(dts, world, device)
             result["split_f16"] = {"ms_per_step": 1000.0 * dts / args.steps,
@@ -796,34 +891,8 @@ def main():
         if dist.is_initialized():
             dist.destroy_process_group()
         return
-    out = {
-        "metric": "depth maps/sec + warp-kernel HBM GB/s, 3-view 640x512 D=192, 1/2/4/8 GPU",
-        "value": result.get("value"),
-        "unit": "depth maps/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_step,
-        "higher_is_better": True,
-        "scaling": "weak" if args.mode == "samples" else "strong",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic N(0,1) images resident in HBM, real DTU scan-1 cameras, random-init "
-                "weights; BN eval mode, live-region regulariser (train-mode BN as in test.py:61: "
-                "field train_bn)",
-        "config": {"workload": "cfg%d: %d-view %dx%d D=%d batch=%d per %s, BN eval, live-region "
-                               "regulariser, fp32 arithmetic" % (
-                       2 if args.mode == "samples" else 4, V, W, H, D, B,
-                       "GPU" if args.mode == "samples" else "job (D sharded)"),
-                   "global_batch": B * (world if args.mode == "samples" else 1),
-                   "views": V, "planes": D, "image_hw": [H, W], "feature_hw": [h, w],
-                   "parallelism": ("samples%d" % world) if args.mode == "samples" else ("dshard%d" % world)},
-        "arithmetic": ("exact fp32 in every layer of the timed step (MVSConfig(arithmetic='fp32'), the default): "
-                       "fp32 cost volume (the reference's torch-CPU law, bit for bit given the sampling matrices), "
-                       "2-D convolutions on fp32 VALU kernels, conv_0_0 / conv_out on fp32 VALU kernels (conv_0_0 "
-                       "with a depth-Winograd F(2,3) transform), every region convolution on the f32-input matrix "
-                       "cores (v_mfma_f32_16x16x4_f32: each product and sum rounded as an fmaf chain), fp32 "
-                       "softmax / soft-argmin / refinement"),
+    out = headline(args, world, B, V, D, H, W, result.get("value"), ms_step)
+    out.update({
         "warp_kernel": {"bound": "hbm", "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                         "frac": gbs / HBM_PEAK_GBS,
                         "traffic": None if traffic is None else traffic.get("hbm_bytes_per_launch"),
@@ -841,7 +910,7 @@ def main():
                            "packing + reference resampling) + cost_volume_staged kernel" % (
                                "_c4" if store == "c4" else ""),
                      "op_GBps": alg / (op_ms * 1e-3) / 1e9},
-    }
+    })
     if head32_ms is not None:
         # the fp32 step's dominant kernel: conv_0_0 (model.py:101, whole volume) + BN_0 + ReLU on the fp32 VALU
         # and conv_1_0 (model.py:103, 32 -> 16 stride 2 on its live region) + BN_1 + ReLU on the f32-input

@@ -199,7 +199,7 @@ class DepthShardedMVSNet(nn.Module):
     in order: "encoder", "shard_kernel" (this rank's D-slab of the cost volume), "exchange" (the
     owner-targeted point-to-point exchange), "owner_compute" (regulariser + soft-argmin + refinement
     of the owned samples; nothing on a rank that owns none), "gather" (the depth maps to ``dst``).
-    bench.py --mode dshard records a HIP event there, per rank."""
+    bench.py --mode dshard --full records a HIP event there, per rank."""
 
     def __init__(self, net, world, rank, group=None, ops=None, gather=True, dst=0):
         super().__init__()

@@ -12,6 +12,6 @@ step layers 300 python -u tools/fp32_layers.py --only conv_0_0,conv_1_0,conv_hea
 grep -E "ms|equal" $OUT/layers.log
 MVS_FP32_HEAD=0 step layers_nohead 300 python -u tools/fp32_layers.py --only step,step --reps 30
 grep ms $OUT/layers_nohead.log
-step bench 400 python -u bench.py --steps 20 --warmup 5
+step bench 400 python -u bench.py --full --steps 20 --warmup 5
 tail -c 3000 $OUT/bench.log
 exit 0

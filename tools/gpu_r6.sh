@@ -3,7 +3,7 @@
 #   (default: tests smoke bench prof pmc)
 #   tests  full GPU suite (+ parity records under $OUT/parity)
 #   smoke  __graft_entry__.smoke()
-#   bench  python bench.py (N=1 defaults) -> $OUT/bench.json
+#   bench  python bench.py --full (N=1 defaults) -> $OUT/bench.json
 #   prof   rocprofv3 --kernel-trace --stats of a short bench (the roofline agreement source)
 #   pmc    head counters, one counter group per rocprofv3 pass, on tools/hip_reg_layers.py --only cv_head
 #   stress tools/dbg/head_stress.py: repeatability of the head and the split path (raw and with BN)
@@ -24,7 +24,7 @@ if has smoke; then
   echo "smoke rc=$rc"; tail -2 $OUT/smoke.log; [ $rc -ne 0 ] && exit $rc
 fi
 if has bench; then
-  s=$(date +%s); timeout -k 10 900 python bench.py ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err; rc=$?
+  s=$(date +%s); timeout -k 10 900 python bench.py --full ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err; rc=$?
   echo "bench rc=$rc wall=$(( $(date +%s) - s ))s"
   if [ $rc -ne 0 ]; then tail -20 $OUT/bench.err; exit $rc; fi
   python3 - $OUT/bench.json <<'PY'
@@ -39,7 +39,7 @@ PY
 fi
 if has prof; then
   timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$GRAFT_REPO_ROOT/$OUT/prof" -o run --output-format csv -- \
-    python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extra --no-train-step > $OUT/prof_bench.json 2> $OUT/prof_bench.err
+    python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-extra --no-train-step > $OUT/prof_bench.json 2> $OUT/prof_bench.err
   rc=$?; echo "prof rc=$rc"; [ $rc -ne 0 ] && exit $rc
   f=$(ls $OUT/prof/*/run_kernel_stats.csv $OUT/prof/run_kernel_stats.csv 2>/dev/null | head -1); head -14 "$f" | cut -c1-160
 fi

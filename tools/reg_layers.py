@@ -8,7 +8,7 @@ import sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "deep-multiview-depth-estimation_amd"))
-import bench  # noqa: E402,F401  (MIOPEN_USER_DB_PATH -> tools/miopen_db)
+import bench  # noqa: E402,F401  (MIOPEN_USER_DB_PATH -> a working copy of tools/miopen_db)
 import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402,F401
 from mvs_amd import model as M  # noqa: E402
