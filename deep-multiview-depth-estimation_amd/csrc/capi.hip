@@ -13,8 +13,8 @@ namespace {
 
 using mvs::Geometry;
 
-// store_es: output element bytes of the packed (2 <= V <= 8) fused kernel this geometry feeds (4 fp32
-// NCDHW, 2 bf16, 16 channel-quad), 0 for entry points that build no cost-volume store descriptors
+// store_es: output element bytes of the packed (2 <= V <= 8) fused kernel this geometry feeds
+// (element_bytes(CvStore)), 0 for entry points that build no cost-volume store descriptors
 int check_geometry(int B, int V, int C, int h, int w, int d_count, Geometry& g, int store_es = 0) {
   if (B <= 0 || C <= 0 || h < 2 || w < 2 || d_count <= 0) return MVS_ERR_INVALID_ARGUMENT;
   if (V < 1 || V > MVS_MAX_VIEWS) return MVS_ERR_UNSUPPORTED_VIEWS;
@@ -45,16 +45,73 @@ bool cams_ok(const float* K, const float* R, const float* T, const float* d_min,
   return K && R && T && d_min && d_int;
 }
 
-// Fused warp + variance into an fp32 (es = 4) or bf16 (es = 2) NCDHW cost volume, or the channel-quad
-// layout in fp32 (es = 16) or bf16 (es = 8).
+// BN scale, shift and mean come as a triple or not at all
+bool bn_all_or_none(const float* a, const float* b, const float* c) {
+  return !((a != nullptr) != (b != nullptr) || (a != nullptr) != (c != nullptr));
+}
+
+// two pointers that come as a pair or not at all
+bool both_or_neither(const void* p, const void* q) { return (p != nullptr) == (q != nullptr); }
+
+// a weight / operand scale exponent split_scale() can have produced
+bool exp_ok(int e) { return e >= -120 && e <= 120; }
+
+// the box origin + [0, size) lies inside the outputs of conv3d(k 3, stride 2, padding pad) over n:
+// (n + 2 pad - 3) / 2 + 1 per dim
+bool s2_region_ok(int origin, int size, int n, int pad) { return origin + size <= (n + 2 * pad - 3) / 2 + 1; }
+
+// The split-fp16 weight scale (csrc/split.h): 2^ew with max|w| 2^ew < 2^14, clamped to [-120, 120];
+// all-zero weights: ew = 0.  false on a non-finite weight.
+bool split_scale(const float* w, size_t n, int* ew) {
+  float m = 0.0f;
+  for (size_t k = 0; k < n; ++k) {
+    if (!std::isfinite(w[k])) return false;
+    m = std::max(m, std::fabs(w[k]));
+  }
+  int e = 0;
+  if (m > 0.0f) (void)std::frexp(m, &e);
+  *ew = m > 0.0f ? std::min(std::max(14 - e, -120), 120) : 0;
+  return true;
+}
+
+// The split of a scaled weight (csrc/split.h): hi = fp16(v), lo = fp16(v - hi), as bit patterns.
+struct SplitBits { uint16_t hi, lo; };
+SplitBits split_bits(float v) {
+  const _Float16 hi = (_Float16)v;
+  const _Float16 lo = (_Float16)(v - (float)hi);
+  SplitBits b;
+  std::memcpy(&b.hi, &hi, 2);
+  std::memcpy(&b.lo, &lo, 2);
+  return b;
+}
+
+// The cost-volume store of the fused warp + variance kernels
+enum class CvStore { kF32, kBf16, kQuadF32, kQuadSplit, kQuadBf16 };
+
+// channel-quad layout [B][C/4][D][h][w][4] (else NCDHW)
+bool is_quad(CvStore s) { return s == CvStore::kQuadF32 || s == CvStore::kQuadSplit || s == CvStore::kQuadBf16; }
+
+// bytes per stored element: an fp32 / bf16 value, or a quad of them (the split quad: 4 hi + 4 lo fp16)
+int element_bytes(CvStore s) {
+  switch (s) {
+    case CvStore::kF32: return 4;
+    case CvStore::kBf16: return 2;
+    case CvStore::kQuadBf16: return 8;
+    case CvStore::kQuadF32:
+    case CvStore::kQuadSplit: return 16;
+  }
+  return 0;   // not reached: every store kind is named above (-Wswitch flags a missing one)
+}
+
+// Fused warp + variance into the cost volume ``store`` describes.
 int cost_volume_fwd_impl(const float* feat, const float* K, const float* R, const float* T,
                          const float* d_min, const float* d_int, int batch_size, int n_views,
                          int channels, int h, int w, int d_begin, int d_count, float d_scale,
-                         float* workspace, void* cv_out, int es, void* stream, void* ev0, void* ev1,
+                         float* workspace, void* cv_out, CvStore store, void* stream, void* ev0, void* ev1,
                          uint32_t* absmax = nullptr) {
   if (!feat || !workspace || !cv_out) return MVS_ERR_INVALID_ARGUMENT;
   Geometry g;
-  int st = check_geometry(batch_size, n_views, channels, h, w, d_count, g, es == 17 ? 16 : es);
+  int st = check_geometry(batch_size, n_views, channels, h, w, d_count, g, element_bytes(store));
   if (st != MVS_OK) return st;
   if (!cams_ok(K, R, T, d_min, d_int) || d_begin < 0) return MVS_ERR_INVALID_ARGUMENT;
   const mvs::LaunchCheck lc;
@@ -64,8 +121,8 @@ int cost_volume_fwd_impl(const float* feat, const float* K, const float* R, cons
     st = mvs_plane_sampling(K, R, T, d_min, d_int, batch_size, n_views, h, w, d_begin, d_count,
                             d_scale, workspace, stream);
     if (st != MVS_OK) return st;
-    const size_t ch = (es == 16 || es == 17 || es == 8) ? (size_t)((channels + 3) / 4) : (size_t)channels;
-    if (hipMemsetAsync(cv_out, 0, (size_t)batch_size * ch * d_count * h * w * (es == 17 ? 16 : es), s) != hipSuccess)
+    const size_t ch = is_quad(store) ? (size_t)((channels + 3) / 4) : (size_t)channels;
+    if (hipMemsetAsync(cv_out, 0, (size_t)batch_size * ch * d_count * h * w * element_bytes(store), s) != hipSuccess)
       return MVS_ERR_HIP;
     return lc.status();
   }
@@ -73,18 +130,23 @@ int cost_volume_fwd_impl(const float* feat, const float* K, const float* R, cons
       reinterpret_cast<char*>(workspace) +
       mvs::align256((size_t)batch_size * n_views * d_count * 9 * sizeof(float)));
   const mvs::Cams cm{K, R, T, d_min, d_int, d_begin, d_scale};
-  if (es == 4)
-    mvs::launch_cost_volume_fwd(g, feat, cm, workspace, packed, static_cast<float*>(cv_out), s,
-                                (hipEvent_t)ev0, (hipEvent_t)ev1);
-  else if (es == 16 || es == 17)   // 17: the split cost volume (16-byte elements)
-    mvs::launch_cost_volume_fwd_c4(g, feat, cm, workspace, packed, static_cast<float*>(cv_out), s,
-                                   (hipEvent_t)ev0, (hipEvent_t)ev1, absmax, es == 17);
-  else if (es == 8)
-    mvs::launch_cost_volume_fwd_c4_bf16(g, feat, cm, workspace, packed, cv_out, s, (hipEvent_t)ev0,
-                                        (hipEvent_t)ev1);
-  else
-    mvs::launch_cost_volume_fwd_bf16(g, feat, cm, workspace, packed, cv_out, s, (hipEvent_t)ev0,
-                                     (hipEvent_t)ev1);
+  hipEvent_t e0 = (hipEvent_t)ev0, e1 = (hipEvent_t)ev1;
+  switch (store) {
+    case CvStore::kF32:
+      mvs::launch_cost_volume_fwd(g, feat, cm, workspace, packed, static_cast<float*>(cv_out), s, e0, e1);
+      break;
+    case CvStore::kQuadF32:
+    case CvStore::kQuadSplit:
+      mvs::launch_cost_volume_fwd_c4(g, feat, cm, workspace, packed, static_cast<float*>(cv_out), s, e0, e1, absmax,
+                                     store == CvStore::kQuadSplit);
+      break;
+    case CvStore::kQuadBf16:
+      mvs::launch_cost_volume_fwd_c4_bf16(g, feat, cm, workspace, packed, cv_out, s, e0, e1);
+      break;
+    case CvStore::kBf16:
+      mvs::launch_cost_volume_fwd_bf16(g, feat, cm, workspace, packed, cv_out, s, e0, e1);
+      break;
+  }
   return lc.status();
 }
 
@@ -136,7 +198,7 @@ int mvs_cost_volume_fwd_timed(const float* feat, const float* K, const float* R,
                               float* workspace, float* cv_out, void* stream,
                               void* main_begin_event, void* main_end_event) {
   return cost_volume_fwd_impl(feat, K, R, T, d_min, d_int, batch_size, n_views, channels, h, w,
-                              d_begin, d_count, d_scale, workspace, cv_out, 4, stream,
+                              d_begin, d_count, d_scale, workspace, cv_out, CvStore::kF32, stream,
                               main_begin_event, main_end_event);
 }
 
@@ -145,7 +207,7 @@ int mvs_cost_volume_fwd(const float* feat, const float* K, const float* R, const
                         int channels, int h, int w, int d_begin, int d_count, float d_scale,
                         float* workspace, float* cv_out, void* stream) {
   return cost_volume_fwd_impl(feat, K, R, T, d_min, d_int, batch_size, n_views, channels, h, w,
-                              d_begin, d_count, d_scale, workspace, cv_out, 4, stream, nullptr,
+                              d_begin, d_count, d_scale, workspace, cv_out, CvStore::kF32, stream, nullptr,
                               nullptr);
 }
 
@@ -155,7 +217,7 @@ int mvs_cost_volume_fwd_bf16(const float* feat, const float* K, const float* R, 
                              float* workspace, void* cv_out, void* stream) {
   if (n_views > 8) return MVS_ERR_UNSUPPORTED_VIEWS;
   return cost_volume_fwd_impl(feat, K, R, T, d_min, d_int, batch_size, n_views, channels, h, w,
-                              d_begin, d_count, d_scale, workspace, cv_out, 2, stream, nullptr,
+                              d_begin, d_count, d_scale, workspace, cv_out, CvStore::kBf16, stream, nullptr,
                               nullptr);
 }
 
@@ -167,7 +229,7 @@ int mvs_cost_volume_fwd_c4(const float* feat, const float* K, const float* R, co
   if (n_views > 8) return MVS_ERR_UNSUPPORTED_VIEWS;
   if ((uintptr_t)cv_out & 15u) return MVS_ERR_INVALID_ARGUMENT;
   return cost_volume_fwd_impl(feat, K, R, T, d_min, d_int, batch_size, n_views, channels, h, w,
-                              d_begin, d_count, d_scale, workspace, cv_out, 16, stream,
+                              d_begin, d_count, d_scale, workspace, cv_out, CvStore::kQuadF32, stream,
                               main_begin_event, main_end_event);
 }
 
@@ -179,7 +241,7 @@ int mvs_cost_volume_fwd_c4_absmax(const float* feat, const float* K, const float
   if (n_views > 8) return MVS_ERR_UNSUPPORTED_VIEWS;
   if (((uintptr_t)cv_out & 15u) || !feat_absmax || ((uintptr_t)feat_absmax & 3u)) return MVS_ERR_INVALID_ARGUMENT;
   return cost_volume_fwd_impl(feat, K, R, T, d_min, d_int, batch_size, n_views, channels, h, w,
-                              d_begin, d_count, d_scale, workspace, cv_out, 16, stream,
+                              d_begin, d_count, d_scale, workspace, cv_out, CvStore::kQuadF32, stream,
                               main_begin_event, main_end_event, feat_absmax);
 }
 
@@ -191,21 +253,14 @@ int mvs_cost_volume_fwd_c4_split(const float* feat, const float* K, const float*
   if (n_views > 8) return MVS_ERR_UNSUPPORTED_VIEWS;
   if (((uintptr_t)cv_out & 15u) || !feat_absmax || ((uintptr_t)feat_absmax & 3u)) return MVS_ERR_INVALID_ARGUMENT;
   return cost_volume_fwd_impl(feat, K, R, T, d_min, d_int, batch_size, n_views, channels, h, w,
-                              d_begin, d_count, d_scale, workspace, cv_out, 17, stream,
+                              d_begin, d_count, d_scale, workspace, cv_out, CvStore::kQuadSplit, stream,
                               main_begin_event, main_end_event, feat_absmax);
 }
 
 int mvs_conv3d_split_weights(const float* weight, unsigned short* frag, int* weight_exp) {
   if (!weight || !frag || !weight_exp) return MVS_ERR_INVALID_ARGUMENT;
-  // scale 2^ew with max|w| 2^ew < 2^14 (all-zero weights: ew = 0)
-  float m = 0.0f;
-  for (int k = 0; k < 8 * 32 * 27; ++k) {
-    if (!std::isfinite(weight[k])) return MVS_ERR_INVALID_ARGUMENT;
-    m = std::max(m, std::fabs(weight[k]));
-  }
-  int e = 0;
-  if (m > 0.0f) (void)std::frexp(m, &e);
-  const int ew = m > 0.0f ? std::min(std::max(14 - e, -120), 120) : 0;
+  int ew;
+  if (!split_scale(weight, 8 * 32 * 27, &ew)) return MVS_ERR_INVALID_ARGUMENT;
   // frag[tap][lane][j]: lane (c = lane & 15, g = lane >> 4) holds B[k = 8g + j][col c] of the
   // 16x16x32 MFMA, column c < 8 = w_hi of output channel c, c >= 8 = w_lo of channel c - 8, k = input
   // channel; tap = (kz * 3 + ky) * 3 + kx; nn.Conv3d weight [8][32][3][3][3]
@@ -213,12 +268,8 @@ int mvs_conv3d_split_weights(const float* weight, unsigned short* frag, int* wei
     for (int lane = 0; lane < 64; ++lane)
       for (int j = 0; j < 8; ++j) {
         const int c = lane & 15, ci = 8 * (lane >> 4) + j, co = c & 7;
-        const float v = std::ldexp(weight[(co * 32 + ci) * 27 + tap], ew);
-        const _Float16 hi = (_Float16)v;
-        const _Float16 part = c < 8 ? hi : (_Float16)(v - (float)hi);
-        uint16_t bits;
-        std::memcpy(&bits, &part, 2);
-        frag[(tap * 64 + lane) * 8 + j] = bits;
+        const SplitBits b = split_bits(std::ldexp(weight[(co * 32 + ci) * 27 + tap], ew));
+        frag[(tap * 64 + lane) * 8 + j] = c < 8 ? b.hi : b.lo;
       }
   *weight_exp = ew;
   return MVS_OK;
@@ -226,28 +277,17 @@ int mvs_conv3d_split_weights(const float* weight, unsigned short* frag, int* wei
 
 int mvs_conv3d_s2_split_weights(const float* weight, unsigned short* frag, int* weight_exp) {
   if (!weight || !frag || !weight_exp) return MVS_ERR_INVALID_ARGUMENT;
-  float m = 0.0f;
-  for (int k = 0; k < 16 * 32 * 27; ++k) {
-    if (!std::isfinite(weight[k])) return MVS_ERR_INVALID_ARGUMENT;
-    m = std::max(m, std::fabs(weight[k]));
-  }
-  int e = 0;
-  if (m > 0.0f) (void)std::frexp(m, &e);
-  const int ew = m > 0.0f ? std::min(std::max(14 - e, -120), 120) : 0;
+  int ew;
+  if (!split_scale(weight, 16 * 32 * 27, &ew)) return MVS_ERR_INVALID_ARGUMENT;
   // frag[tap][part][lane][j]: lane (c = lane & 15, g = lane >> 4) holds B[k = 8g + j][col c], column
   // c = output channel c, k = input channel; part 0 = hi, 1 = lo; nn.Conv3d weight [16][32][3][3][3]
   for (int tap = 0; tap < 27; ++tap)
     for (int lane = 0; lane < 64; ++lane)
       for (int j = 0; j < 8; ++j) {
         const int co = lane & 15, ci = 8 * (lane >> 4) + j;
-        const float v = std::ldexp(weight[(co * 32 + ci) * 27 + tap], ew);
-        const _Float16 hi = (_Float16)v;
-        const _Float16 lo = (_Float16)(v - (float)hi);
-        uint16_t bh, bl;
-        std::memcpy(&bh, &hi, 2);
-        std::memcpy(&bl, &lo, 2);
-        frag[((tap * 2 + 0) * 64 + lane) * 8 + j] = bh;
-        frag[((tap * 2 + 1) * 64 + lane) * 8 + j] = bl;
+        const SplitBits b = split_bits(std::ldexp(weight[(co * 32 + ci) * 27 + tap], ew));
+        frag[((tap * 2 + 0) * 64 + lane) * 8 + j] = b.hi;
+        frag[((tap * 2 + 1) * 64 + lane) * 8 + j] = b.lo;
       }
   *weight_exp = ew;
   return MVS_OK;
@@ -262,14 +302,12 @@ int mvs_conv3d_s2_split_fwd(const void* x, int flags, const void* weight_frag, i
   if ((flags & ~MVS_CONV_IN_SPLIT) || ((flags & MVS_CONV_IN_SPLIT) && !x_absmax)) return MVS_ERR_INVALID_ARGUMENT;
   if (((uintptr_t)x & 15u) || ((uintptr_t)weight_frag & 15u) || ((uintptr_t)x_absmax & 3u))
     return MVS_ERR_INVALID_ARGUMENT;
-  if ((bn_scale != nullptr) != (bn_shift != nullptr) || (bn_scale != nullptr) != (bn_mean != nullptr))
-    return MVS_ERR_INVALID_ARGUMENT;
-  if (weight_exp < -120 || weight_exp > 120) return MVS_ERR_INVALID_ARGUMENT;
+  if (!bn_all_or_none(bn_scale, bn_shift, bn_mean)) return MVS_ERR_INVALID_ARGUMENT;
+  if (!exp_ok(weight_exp)) return MVS_ERR_INVALID_ARGUMENT;
   uint64_t vox = 1, ovox = 1;
   for (int d = 0; d < 3; ++d) {
     if (dims[d] <= 0 || out_size[d] <= 0 || out_origin[d] < 0 || pad[d] < 0) return MVS_ERR_INVALID_ARGUMENT;
-    // outputs of conv3d(stride 2, padding pad): (n + 2 pad - 3) / 2 + 1 per dim
-    if (out_origin[d] + out_size[d] > (dims[d] + 2 * pad[d] - 3) / 2 + 1) return MVS_ERR_INVALID_ARGUMENT;
+    if (!s2_region_ok(out_origin[d], out_size[d], dims[d], pad[d])) return MVS_ERR_INVALID_ARGUMENT;
     vox *= (uint64_t)dims[d];
     ovox *= (uint64_t)out_size[d];
   }
@@ -298,10 +336,9 @@ int mvs_cost_volume_head_fwd(const float* feat, const float* K, const float* R, 
   if (channels != 32 || (d_count & 1)) return MVS_ERR_INVALID_ARGUMENT;
   if ((((uintptr_t)w0_frag) | ((uintptr_t)w1_frag) | ((uintptr_t)y0) | ((uintptr_t)scv)) & 15u) return MVS_ERR_INVALID_ARGUMENT;
   if (((uintptr_t)feat_absmax) & 3u) return MVS_ERR_INVALID_ARGUMENT;
-  if ((bn0_scale != nullptr) != (bn0_shift != nullptr) || (bn0_scale != nullptr) != (bn0_mean != nullptr) ||
-      (bn1_scale != nullptr) != (bn1_shift != nullptr) || (bn1_scale != nullptr) != (bn1_mean != nullptr))
+  if (!bn_all_or_none(bn0_scale, bn0_shift, bn0_mean) || !bn_all_or_none(bn1_scale, bn1_shift, bn1_mean))
     return MVS_ERR_INVALID_ARGUMENT;
-  if (w0_exp < -120 || w0_exp > 120 || w1_exp < -120 || w1_exp > 120) return MVS_ERR_INVALID_ARGUMENT;
+  if (!exp_ok(w0_exp) || !exp_ok(w1_exp)) return MVS_ERR_INVALID_ARGUMENT;
   Geometry g;
   int st = check_geometry(batch_size, n_views, channels, h, w, d_count, g, 16);
   if (st != MVS_OK) return st;
@@ -309,7 +346,7 @@ int mvs_cost_volume_head_fwd(const float* feat, const float* K, const float* R, 
   uint64_t ovox = 1;
   for (int d = 0; d < 3; ++d) {
     if (pad[d] < 1 || !(pad[d] & 1)) return MVS_ERR_INVALID_ARGUMENT;
-    if (y1_size[d] <= 0 || y1_origin[d] < 0 || y1_origin[d] + y1_size[d] > (n[d] + 2 * pad[d] - 3) / 2 + 1)
+    if (y1_size[d] <= 0 || y1_origin[d] < 0 || !s2_region_ok(y1_origin[d], y1_size[d], n[d], pad[d]))
       return MVS_ERR_INVALID_ARGUMENT;
     if (scv_lo[d] < 0 || scv_hi[d] > n[d] || scv_lo[d] > scv_hi[d]) return MVS_ERR_INVALID_ARGUMENT;
     ovox *= (uint64_t)y1_size[d];
@@ -343,30 +380,21 @@ int mvs_split_head_fwd(const void* scv, const unsigned* x_absmax, int batch, int
   if ((((uintptr_t)scv) | ((uintptr_t)w0_frag) | ((uintptr_t)w1_frag) | ((uintptr_t)y0)) & 15u ||
       ((uintptr_t)x_absmax & 3u))
     return MVS_ERR_INVALID_ARGUMENT;
-  if ((bn0_scale != nullptr) != (bn0_shift != nullptr) || (bn0_scale != nullptr) != (bn0_mean != nullptr) ||
-      (bn1_scale != nullptr) != (bn1_shift != nullptr) || (bn1_scale != nullptr) != (bn1_mean != nullptr))
+  if (!bn_all_or_none(bn0_scale, bn0_shift, bn0_mean) || !bn_all_or_none(bn1_scale, bn1_shift, bn1_mean))
     return MVS_ERR_INVALID_ARGUMENT;
-  if (w0_exp < -120 || w0_exp > 120 || w1_exp < -120 || w1_exp > 120) return MVS_ERR_INVALID_ARGUMENT;
+  if (!exp_ok(w0_exp) || !exp_ok(w1_exp)) return MVS_ERR_INVALID_ARGUMENT;
   const int n[3] = {d_count, h, w};
   uint64_t ovox = 1;
   for (int d = 0; d < 3; ++d) {
     if (pad[d] < 1 || !(pad[d] & 1)) return MVS_ERR_INVALID_ARGUMENT;
-    if (y1_size[d] <= 0 || y1_origin[d] < 0 || y1_origin[d] + y1_size[d] > (n[d] + 2 * pad[d] - 3) / 2 + 1)
+    if (y1_size[d] <= 0 || y1_origin[d] < 0 || !s2_region_ok(y1_origin[d], y1_size[d], n[d], pad[d]))
       return MVS_ERR_INVALID_ARGUMENT;
     ovox *= (uint64_t)y1_size[d];
   }
   if (128ull * (uint64_t)d_count * (uint64_t)h * (uint64_t)w > 0xFFFFFFF0ull ||
       (uint64_t)batch * ovox * 16ull >= (1ull << 40))
     return MVS_ERR_TOO_LARGE;
-  mvs::Geometry g;
-  g.B = batch;
-  g.V = 2;
-  g.C = 32;
-  g.h = h;
-  g.w = w;
-  g.Dc = d_count;
-  g.tiles = 0;
-  g.total = 0;
+  const Geometry g{batch, 2, 32, h, w, d_count, 0, 0};   // B, V, C, h, w, Dc, tiles, total
   const mvs::LaunchCheck lc;
   const float* bn0[3] = {bn0_scale, bn0_shift, bn0_mean};
   const float* bn1[3] = {bn1_scale, bn1_shift, bn1_mean};
@@ -384,9 +412,8 @@ int mvs_conv3d_k3_split_fwd(const void* x, int flags, const void* weight_frag, i
   if ((flags & ~MVS_CONV_IN_SPLIT) || ((flags & MVS_CONV_IN_SPLIT) && !x_absmax)) return MVS_ERR_INVALID_ARGUMENT;
   if (((uintptr_t)x & 15u) || ((uintptr_t)weight_frag & 15u) || ((uintptr_t)x_absmax & 3u))
     return MVS_ERR_INVALID_ARGUMENT;
-  if ((bn_scale != nullptr) != (bn_shift != nullptr) || (bn_scale != nullptr) != (bn_mean != nullptr))
-    return MVS_ERR_INVALID_ARGUMENT;
-  if (weight_exp < -120 || weight_exp > 120) return MVS_ERR_INVALID_ARGUMENT;
+  if (!bn_all_or_none(bn_scale, bn_shift, bn_mean)) return MVS_ERR_INVALID_ARGUMENT;
+  if (!exp_ok(weight_exp)) return MVS_ERR_INVALID_ARGUMENT;
   // one 32-bit buffer descriptor per sample volume (8 quads of 16 B per voxel) and 32-bit staging offsets
   if (128ull * (uint64_t)d * (uint64_t)h * (uint64_t)w > 0xFFFFFFF0ull) return MVS_ERR_TOO_LARGE;
   const mvs::LaunchCheck lc;
@@ -403,7 +430,7 @@ int mvs_cost_volume_fwd_c4_bf16(const float* feat, const float* K, const float* 
   if (n_views > 8) return MVS_ERR_UNSUPPORTED_VIEWS;
   if ((uintptr_t)cv_out & 7u) return MVS_ERR_INVALID_ARGUMENT;
   return cost_volume_fwd_impl(feat, K, R, T, d_min, d_int, batch_size, n_views, channels, h, w,
-                              d_begin, d_count, d_scale, workspace, cv_out, 8, stream,
+                              d_begin, d_count, d_scale, workspace, cv_out, CvStore::kQuadBf16, stream,
                               main_begin_event, main_end_event);
 }
 
@@ -500,8 +527,7 @@ int mvs_conv2d_fwd(const float* x, const float* weight, float* y, int n, int c_i
                    int k, int stride, const float* bn_scale, const float* bn_shift, const float* bn_mean,
                    unsigned* y_bound, void* stream) {
   if (!x || !weight || !y || n <= 0 || n > 65535 || h <= 0 || w <= 0 || stride <= 0) return MVS_ERR_INVALID_ARGUMENT;
-  if ((bn_scale != nullptr) != (bn_shift != nullptr) || (bn_scale != nullptr) != (bn_mean != nullptr))
-    return MVS_ERR_INVALID_ARGUMENT;
+  if (!bn_all_or_none(bn_scale, bn_shift, bn_mean)) return MVS_ERR_INVALID_ARGUMENT;
   // staging offsets inside one image are 32-bit
   if ((uint64_t)c_in * (uint64_t)h * (uint64_t)w >= (1ull << 31)) return MVS_ERR_TOO_LARGE;
   const mvs::LaunchCheck lc;
@@ -514,25 +540,14 @@ int mvs_conv2d_split_weights(const float* weight, int c_in, int c_out, int k, un
   if (!weight || !frag || !weight_exp || k <= 0 || k > 7) return MVS_ERR_INVALID_ARGUMENT;
   if (!(c_in == 8 || c_in == 16 || c_in == 32) || !(c_out == 8 || (c_out > 0 && c_out % 16 == 0)))
     return MVS_ERR_INVALID_ARGUMENT;
-  const int taps = k * k, n = c_out * c_in * taps;
-  float m = 0.0f;
-  for (int i = 0; i < n; ++i) {
-    if (!std::isfinite(weight[i])) return MVS_ERR_INVALID_ARGUMENT;
-    m = std::max(m, std::fabs(weight[i]));
-  }
-  int e = 0;
-  if (m > 0.0f) (void)std::frexp(m, &e);
-  const int ew = m > 0.0f ? std::min(std::max(14 - e, -120), 120) : 0;
+  const int taps = k * k;
+  int ew;
+  if (!split_scale(weight, (size_t)c_out * c_in * taps, &ew)) return MVS_ERR_INVALID_ARGUMENT;
   const int kbs = mvs::conv2d_split_kblocks(c_in, k), tpb = 32 / c_in, cpt = c_in / 8;
   const bool narrow = c_out == 8;
   const int nbs = narrow ? 1 : c_out / 16;
-  auto part = [&](int co, int ci, int t, int p) -> uint16_t {
-    const float v = t < taps ? std::ldexp(weight[((size_t)co * c_in + ci) * taps + t], ew) : 0.0f;
-    const _Float16 hi = (_Float16)v;
-    const _Float16 r = p == 0 ? hi : (_Float16)(v - (float)hi);
-    uint16_t b;
-    std::memcpy(&b, &r, 2);
-    return b;
+  auto split = [&](int co, int ci, int t) {   // taps past k * k pad the last K block with zeros
+    return split_bits(t < taps ? std::ldexp(weight[((size_t)co * c_in + ci) * taps + t], ew) : 0.0f);
   };
   for (int kb = 0; kb < kbs; ++kb)
     for (int nb = 0; nb < nbs; ++nb)
@@ -540,12 +555,13 @@ int mvs_conv2d_split_weights(const float* weight, int c_in, int c_out, int k, un
         for (int j = 0; j < 8; ++j) {
           const int c = lane & 15, g = lane >> 4;
           const int t = kb * tpb + g / cpt, ci = 8 * (g % cpt) + j;
-          if (narrow) {
-            frag[((size_t)kb * 64 + lane) * 8 + j] = part(c & 7, ci, t, c >> 3);
+          const SplitBits b = split(narrow ? c & 7 : nb * 16 + c, ci, t);
+          if (narrow) {   // columns 0..7 hi, 8..15 lo of the 8 output channels
+            frag[((size_t)kb * 64 + lane) * 8 + j] = c < 8 ? b.hi : b.lo;
           } else {
             const size_t base = ((((size_t)kb * nbs + nb) * 2) * 64 + lane) * 8 + j;
-            frag[base] = part(nb * 16 + c, ci, t, 0);
-            frag[base + 64 * 8] = part(nb * 16 + c, ci, t, 1);
+            frag[base] = b.hi;
+            frag[base + 64 * 8] = b.lo;
           }
         }
   *weight_exp = ew;
@@ -557,8 +573,7 @@ int mvs_conv2d_split_fwd(const float* x, const void* weight_frag, int weight_exp
                          const float* bn_mean, const unsigned* x_bound, unsigned* y_bound, void* stream) {
   if (!x || !weight_frag || !y || !x_bound || n <= 0 || n > 65535 || h <= 0 || w <= 0 || stride <= 0)
     return MVS_ERR_INVALID_ARGUMENT;
-  if ((bn_scale != nullptr) != (bn_shift != nullptr) || (bn_scale != nullptr) != (bn_mean != nullptr))
-    return MVS_ERR_INVALID_ARGUMENT;
+  if (!bn_all_or_none(bn_scale, bn_shift, bn_mean)) return MVS_ERR_INVALID_ARGUMENT;
   if (reinterpret_cast<uintptr_t>(weight_frag) % 16) return MVS_ERR_INVALID_ARGUMENT;
   // one image's buffer resource and staging offsets are 32-bit
   if ((uint64_t)c_in * (uint64_t)h * (uint64_t)w * 4u >= (1ull << 31)) return MVS_ERR_TOO_LARGE;
@@ -581,8 +596,7 @@ int mvs_conv3d_k3_fwd(const float* x, int flags, const float* weight, float* y, 
   if ((flags & MVS_CONV_WINO_Z) && c_out != 8) return MVS_ERR_INVALID_ARGUMENT;
   if ((flags & MVS_CONV_IN_C4) && (c_in % 4 || (!(flags & MVS_CONV_IN_BF16) && ((uintptr_t)x & 15u))))
     return MVS_ERR_INVALID_ARGUMENT;
-  if ((bn_scale != nullptr) != (bn_shift != nullptr) || (bn_scale != nullptr) != (bn_mean != nullptr))
-    return MVS_ERR_INVALID_ARGUMENT;
+  if (!bn_all_or_none(bn_scale, bn_shift, bn_mean)) return MVS_ERR_INVALID_ARGUMENT;
   // staging offsets inside one channel volume are 32-bit
   if ((uint64_t)d * (uint64_t)h * (uint64_t)w >= (1ull << 31)) return MVS_ERR_TOO_LARGE;
   const mvs::LaunchCheck lc;
@@ -619,8 +633,7 @@ int mvs_conv_head_fp32_fwd(const float* cv4, int batch, int d, int h, int w, con
       h <= 0 || w <= 0)
     return MVS_ERR_INVALID_ARGUMENT;
   if (((uintptr_t)cv4 | (uintptr_t)w1 | (uintptr_t)w1_pass) & 15u) return MVS_ERR_INVALID_ARGUMENT;
-  if ((bn0_scale != nullptr) != (bn0_shift != nullptr) || (bn0_scale != nullptr) != (bn0_mean != nullptr) ||
-      (bn1_scale != nullptr) != (bn1_shift != nullptr) || (bn1_scale != nullptr) != (bn1_mean != nullptr))
+  if (!bn_all_or_none(bn0_scale, bn0_shift, bn0_mean) || !bn_all_or_none(bn1_scale, bn1_shift, bn1_mean))
     return MVS_ERR_INVALID_ARGUMENT;
   const int n[3] = {d, h, w};
   uint64_t ovox = (uint64_t)batch;
@@ -649,8 +662,7 @@ int mvs_deconv3d_k3s2_fwd(const float* x, const float* x2, int flags, int batch,
     return MVS_ERR_INVALID_ARGUMENT;   // 16-byte channel-quad loads
   if (rd <= 0 || rh <= 0 || rw <= 0 || d <= 0 || h <= 0 || w <= 0) return MVS_ERR_INVALID_ARGUMENT;
   if (x0d < 0 || x0h < 0 || x0w < 0 || pd < 0 || ph < 0 || pw < 0) return MVS_ERR_INVALID_ARGUMENT;
-  if ((bn_scale != nullptr) != (bn_shift != nullptr) || (bn_scale != nullptr) != (bn_mean != nullptr))
-    return MVS_ERR_INVALID_ARGUMENT;
+  if (!bn_all_or_none(bn_scale, bn_shift, bn_mean)) return MVS_ERR_INVALID_ARGUMENT;
   // the region input is read through 32-bit buffer descriptors over the whole batch
   if ((uint64_t)batch * c_in * rd * rh * rw * 4u >= (1ull << 31)) return MVS_ERR_TOO_LARGE;
   const int layout = (flags & MVS_LAYOUT_CHANNELS_LAST) ? ((flags & MVS_DECONV_WEIGHT_TAPS) ? 3 : 1)
@@ -680,12 +692,11 @@ int mvs_conv3d_region_fwd(int mode, int flags, const float* x, const float* x2, 
     return MVS_ERR_INVALID_ARGUMENT;
   if ((flags & MVS_CONV_IN_C4) && (mode != MVS_CONV_S2 || c_in % 4)) return MVS_ERR_INVALID_ARGUMENT;
   if (mode != MVS_CONV_S2 && (!in_origin || !in_size)) return MVS_ERR_INVALID_ARGUMENT;
-  if ((in_origin != nullptr) != (in_size != nullptr)) return MVS_ERR_INVALID_ARGUMENT;
+  if (!both_or_neither(in_origin, in_size)) return MVS_ERR_INVALID_ARGUMENT;
   const bool boxed = in_origin != nullptr;   // S2: x holds the box [in_origin, + in_size) of the volume
   if (mode != MVS_CONV_S1 && !pad) return MVS_ERR_INVALID_ARGUMENT;
   if (((uintptr_t)x | (uintptr_t)x2 | (uintptr_t)weight) & 15u) return MVS_ERR_INVALID_ARGUMENT;   // 16-byte loads
-  if ((bn_scale != nullptr) != (bn_shift != nullptr) || (bn_scale != nullptr) != (bn_mean != nullptr))
-    return MVS_ERR_INVALID_ARGUMENT;
+  if (!bn_all_or_none(bn_scale, bn_shift, bn_mean)) return MVS_ERR_INVALID_ARGUMENT;
   uint64_t ovox = (uint64_t)batch, ivox = (uint64_t)batch, nvox = (uint64_t)batch * c_in;
   for (int k = 0; k < 3; ++k) {
     if (dims[k] <= 0 || out_size[k] <= 0 || out_origin[k] < 0 || out_origin[k] + out_size[k] > dims[k])
@@ -720,15 +731,8 @@ int mvs_conv3d_region_fwd(int mode, int flags, const float* x, const float* x2, 
 int mvs_conv3d_region_split_weights(const float* weight, int c_in, int c_out, unsigned short* frag, int* weight_exp) {
   if (!weight || !frag || !weight_exp) return MVS_ERR_INVALID_ARGUMENT;
   if (c_out <= 0 || c_out % 16 || !(c_in == 16 || (c_in > 0 && c_in % 32 == 0))) return MVS_ERR_INVALID_ARGUMENT;
-  const int n = 27 * c_out * c_in;
-  float m = 0.0f;
-  for (int k = 0; k < n; ++k) {
-    if (!std::isfinite(weight[k])) return MVS_ERR_INVALID_ARGUMENT;
-    m = std::max(m, std::fabs(weight[k]));
-  }
-  int e = 0;
-  if (m > 0.0f) (void)std::frexp(m, &e);
-  const int ew = m > 0.0f ? std::min(std::max(14 - e, -120), 120) : 0;
+  int ew;
+  if (!split_scale(weight, (size_t)27 * c_out * c_in, &ew)) return MVS_ERR_INVALID_ARGUMENT;
   // frag[kb][nb][part][lane][j]: lane (c = lane & 15, g = lane >> 4) holds B[k = 8g + j][column c] of the
   // 16x16x32 MFMA for output channel nb * 16 + c; part 0 = fp16(w 2^ew), 1 = fp16(w 2^ew - part 0).
   // K block kb: c_in >= 32: tap kb / (c_in / 32), input channel (kb % (c_in / 32)) * 32 + 8g + j;
@@ -747,15 +751,11 @@ int mvs_conv3d_region_split_weights(const float* weight, int c_in, int c_out, un
             tap = kb / (c_in / 32);
             ci = (kb % (c_in / 32)) * 32 + 8 * gq + j;
           }
-          const float v = tap < 27 ? std::ldexp(weight[((size_t)tap * c_out + co) * c_in + ci], ew) : 0.0f;
-          const _Float16 hi = (_Float16)v;
-          const _Float16 lo = (_Float16)(v - (float)hi);
-          uint16_t bh, bl;
-          std::memcpy(&bh, &hi, 2);
-          std::memcpy(&bl, &lo, 2);
+          const SplitBits b =
+              split_bits(tap < 27 ? std::ldexp(weight[((size_t)tap * c_out + co) * c_in + ci], ew) : 0.0f);
           const size_t base = ((((size_t)kb * nbs + nb) * 2) * 64 + lane) * 8 + j;
-          frag[base] = bh;
-          frag[base + 64 * 8] = bl;
+          frag[base] = b.hi;
+          frag[base + 64 * 8] = b.lo;
         }
   *weight_exp = ew;
   return MVS_OK;
@@ -769,7 +769,7 @@ int mvs_conv3d_region_split_fwd(int mode, int flags, const float* x, const float
                                 const float* y_addend, const int* store_origin, const int* store_size, double* stats,
                                 float* y_mid, float* y_high, const float* in_bn, void* stream) {
   if (!x || !weight_frag || !y || !dims || !out_origin || !out_size || batch <= 0) return MVS_ERR_INVALID_ARGUMENT;
-  if ((store_origin != nullptr) != (store_size != nullptr) || ((uintptr_t)stats & 7u) || ((uintptr_t)in_bn & 15u))
+  if (!both_or_neither(store_origin, store_size) || ((uintptr_t)stats & 7u) || ((uintptr_t)in_bn & 15u))
     return MVS_ERR_INVALID_ARGUMENT;
   if (store_origin)   // the store box lies inside the output region
     for (int k = 0; k < 3; ++k)
@@ -784,7 +784,7 @@ int mvs_conv3d_region_split_fwd(int mode, int flags, const float* x, const float
   const int in_flags = MVS_CONV_IN_C4 | MVS_CONV_IN_SPLIT;
   if (s2 != ((flags & in_flags) == in_flags) || (!s2 && (flags & in_flags))) return MVS_ERR_INVALID_ARGUMENT;
   if (s2 && (x2 || !x_bound || c_in != 32)) return MVS_ERR_INVALID_ARGUMENT;
-  if ((in_origin != nullptr) != (in_size != nullptr) || (!s2 && !in_origin)) return MVS_ERR_INVALID_ARGUMENT;
+  if (!both_or_neither(in_origin, in_size) || (!s2 && !in_origin)) return MVS_ERR_INVALID_ARGUMENT;
   if (mode != MVS_CONV_S1 && !pad) return MVS_ERR_INVALID_ARGUMENT;
   int io[3] = {0, 0, 0}, is[3] = {dims[0], dims[1], dims[2]};   // S2 without a box: the whole volume
   if (in_origin)
@@ -798,9 +798,8 @@ int mvs_conv3d_region_split_fwd(int mode, int flags, const float* x, const float
   if (((uintptr_t)x | (uintptr_t)x2 | (uintptr_t)weight_frag) & 15u ||
       ((uintptr_t)x_bound | (uintptr_t)x2_bound | (uintptr_t)y_bound) & 3u)
     return MVS_ERR_INVALID_ARGUMENT;
-  if (weight_exp < -120 || weight_exp > 120) return MVS_ERR_INVALID_ARGUMENT;
-  if ((bn_scale != nullptr) != (bn_shift != nullptr) || (bn_scale != nullptr) != (bn_mean != nullptr))
-    return MVS_ERR_INVALID_ARGUMENT;
+  if (!exp_ok(weight_exp)) return MVS_ERR_INVALID_ARGUMENT;
+  if (!bn_all_or_none(bn_scale, bn_shift, bn_mean)) return MVS_ERR_INVALID_ARGUMENT;
   uint64_t ovox = (uint64_t)batch, svox = 1;
   for (int k = 0; k < 3; ++k) {
     if (dims[k] <= 0 || out_size[k] <= 0 || out_origin[k] < 0 || out_origin[k] + out_size[k] > dims[k])
@@ -899,7 +898,7 @@ int mvs_bn_train_params(const double* sums, int channels, double count, const do
                         long long* num_batches_tracked, double momentum, double eps, float* params, void* stream) {
   if (!sums || !weight || !bias || !params || channels <= 0 || !(count > 0.0) || !(eps >= 0.0))
     return MVS_ERR_INVALID_ARGUMENT;
-  if ((running_mean != nullptr) != (running_var != nullptr)) return MVS_ERR_INVALID_ARGUMENT;
+  if (!both_or_neither(running_mean, running_var)) return MVS_ERR_INVALID_ARGUMENT;
   if (border_u && (!border_count || !prev_params || prev_channels <= 0 || prev_channels > 256 || classes <= 0 ||
                    (long long)channels * classes > 2048))
     return MVS_ERR_INVALID_ARGUMENT;

@@ -39,6 +39,10 @@ STATUS = {0: "ok", -1: "invalid argument", -2: "unsupported n_views", -3: "too l
 
 _c_int, _c_float, _p = ctypes.c_int, ctypes.c_float, ctypes.c_void_p
 
+# feat, K, R, T, d_min, d_int, batch_size, n_views, channels, h, w, d_begin, d_count, d_scale, workspace, out,
+# stream: what every cost-volume / warp forward entry point starts with
+_CV_ARGS = [_p] * 6 + [_c_int] * 7 + [_c_float, _p, _p, _p]
+
 # name -> (restype, argtypes); mirrors include/mvs_cost_volume.h
 SIGNATURES = {
     "mvs_abi_version": (_c_int, []),
@@ -48,33 +52,24 @@ SIGNATURES = {
                                                            _c_int]),
     "mvs_plane_sampling": (_c_int, [_p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int,
                                     _c_int, _c_float, _p, _p]),
-    "mvs_cost_volume_fwd": (_c_int, [_p, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int,
-                                     _c_int, _c_int, _c_int, _c_float, _p, _p, _p]),
-    "mvs_cost_volume_fwd_timed": (_c_int, [_p, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int,
-                                           _c_int, _c_int, _c_int, _c_float, _p, _p, _p, _p, _p]),
-    "mvs_cost_volume_fwd_c4": (_c_int, [_p, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int,
-                                        _c_int, _c_int, _c_int, _c_float, _p, _p, _p, _p, _p]),
-    "mvs_cost_volume_fwd_c4_absmax": (_c_int, [_p, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int,
-                                               _c_int, _c_int, _c_int, _c_float, _p, _p, _p, _p, _p, _p]),
+    "mvs_cost_volume_fwd": (_c_int, _CV_ARGS),
+    "mvs_cost_volume_fwd_timed": (_c_int, _CV_ARGS + [_p, _p]),             # + the event pair
+    "mvs_cost_volume_fwd_c4": (_c_int, _CV_ARGS + [_p, _p]),
+    "mvs_cost_volume_fwd_c4_absmax": (_c_int, _CV_ARGS + [_p, _p, _p]),     # + the bound words
     "mvs_conv3d_k3_split_fwd": (_c_int, [_p, _c_int, _p, _c_int, _p, _p] + [_c_int] * 4 + [_p] * 4),
-    "mvs_cost_volume_fwd_c4_split": (_c_int, [_p, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int,
-                                              _c_int, _c_int, _c_int, _c_float, _p, _p, _p, _p, _p, _p]),
+    "mvs_cost_volume_fwd_c4_split": (_c_int, _CV_ARGS + [_p, _p, _p]),
     "mvs_conv3d_split_weights": (_c_int, [_p, _p, _p]),
     "mvs_conv3d_s2_split_fwd": (_c_int, [_p, _c_int, _p, _c_int, _p, _p, _c_int] + [_p] * 8),
     "mvs_conv3d_s2_split_weights": (_c_int, [_p, _p, _p]),
     "mvs_split_head_fwd": (_c_int, [_p, _p, _c_int, _c_int, _c_int, _c_int, _p, _c_int, _p, _p, _p,
                                     _p, _c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
-    "mvs_cost_volume_head_fwd": (_c_int, [_p, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int,
-                                          _c_int, _c_int, _c_float,
-                                          _p, _c_int, _p, _p, _p, _p, _c_int, _p, _p, _p,
+    "mvs_cost_volume_head_fwd": (_c_int, _CV_ARGS[:14] +    # feat .. d_scale
+                                         [_p, _c_int, _p, _p, _p, _p, _c_int, _p, _p, _p,
                                           _p, _p, _p, _p, _p,
                                           _p, _p, _p, _p, _p, _p, _p, _p]),
-    "mvs_cost_volume_fwd_c4_bf16": (_c_int, [_p, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int,
-                                             _c_int, _c_int, _c_int, _c_float, _p, _p, _p, _p, _p]),
-    "mvs_cost_volume_fwd_bf16": (_c_int, [_p, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int,
-                                          _c_int, _c_int, _c_int, _c_float, _p, _p, _p]),
-    "mvs_homography_warp_fwd": (_c_int, [_p, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int,
-                                         _c_int, _c_int, _c_int, _c_float, _p, _p, _p]),
+    "mvs_cost_volume_fwd_c4_bf16": (_c_int, _CV_ARGS + [_p, _p]),
+    "mvs_cost_volume_fwd_bf16": (_c_int, _CV_ARGS),
+    "mvs_homography_warp_fwd": (_c_int, _CV_ARGS),
     "mvs_assemble_cost_volume_fwd": (_c_int, [_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
                                               _p, _p]),
     "mvs_cost_volume_bwd_workspace_bytes": (ctypes.c_size_t, [_c_int, _c_int, _c_int, _c_int,

@@ -13,6 +13,7 @@ Every op requires CUDA(HIP) tensors and raises otherwise: there is no CPU path i
 Camera tensors (K, R, T, d_min, d_int) are moved to the feature device here, as the reference
 does with ``.to(DEVICE)`` (homography.py:25,43-58).
 """
+import collections
 import ctypes
 import weakref
 from typing import Optional
@@ -64,42 +65,121 @@ def _check_geometry(feat, K, batch_size, n_views):
         raise ValueError("K holds %d cameras, batch_size*n_views = %d" % (K.shape[0], n))
 
 
+def _ints3(v):
+    return (ctypes.c_int * 3)(*[int(a) for a in v])
+
+
+def _opt_ptr(t):
+    return None if t is None else _lib.ptr(t)
+
+
+def _opt_ints3(v):
+    return None if v is None else _ints3(v)
+
+
+def _bn_triple(scale, shift, mean, device):
+    """(tensors, pointers) of an eval-BN epilogue's (scale, shift, mean): fp32 contiguous on ``device``, all
+    three or none.  The caller holds the tensors until its launch is enqueued (the pointers do not)."""
+    ts = [t if t is None else t.to(device=device, dtype=_F32).contiguous() for t in (scale, shift, mean)]
+    if any(t is None for t in ts) and not all(t is None for t in ts):
+        raise ValueError("bn_scale, bn_shift and bn_mean go together")
+    return ts, [_opt_ptr(t) for t in ts]
+
+
+def _host_fragments(entry, weight, n_int16, *int_args, device):
+    """(int16 [n_int16] split-fp16 MFMA fragments on ``device``, exponent) of ``weight``, formed on the host
+    by the C ABI's own split ``entry``(weight, *int_args, frag, &exponent), so every caller gets the same."""
+    lib = _lib.load()
+    w = weight.detach().to(device="cpu", dtype=_F32).contiguous()
+    frag = torch.empty((n_int16,), dtype=torch.int16)
+    e = ctypes.c_int(0)
+    st = getattr(lib, entry)(_lib.ptr(w), *int_args, _lib.ptr(frag), ctypes.byref(e))
+    _lib.check(st, entry)
+    return frag.to(device), e.value
+
+
+def _cv_prelude(feat, K, R, T, d_min, d_int, batch_size, n_views):
+    """What every op over (feature maps, cameras) starts with: (library, fp32 contiguous feat, the camera
+    tensors on its device), the geometry checked."""
+    _require_gpu(feat, "feature_maps")
+    lib = _lib.load()
+    feat = feat.to(_F32).contiguous()
+    cams = _cams(K, R, T, d_min, d_int, feat.device, batch_size)
+    _check_geometry(feat, cams[0], batch_size, n_views)
+    return lib, feat, cams
+
+
 # ----------------------------------------------------------------------------------------------
 # mvs::cost_volume (+ backward)
 # ----------------------------------------------------------------------------------------------
+def _ws_floats(batch_size, n_views, c, h, w, d_count):
+    """Workspace size in floats, from the library's own size function (host-only, no GPU)."""
+    return max(_lib.load().mvs_cost_volume_workspace_bytes(batch_size, n_views, c, h, w, d_count), 4) // 4
+
+
+def _cv_shape(batch_size, c, d_count, h, w, quad):
+    """The cost volume's shape: NCDHW, or the channel-quad layout."""
+    return (batch_size, c // 4, d_count, h, w, 4) if quad else (batch_size, c, d_count, h, w)
+
+
+# One fused warp + variance op: the C ABI entry point, the output layout (channel-quad or NCDHW) and dtype,
+# whether the int32[8] bound words are produced, and the KERNEL_EVENT_HOOK kind of the entries that take an
+# event pair (None: the entry has no event arguments)
+_CvOp = collections.namedtuple("_CvOp", "entry quad dtype bound kind")
+_CV_OPS = {
+    "cost_volume": _CvOp("mvs_cost_volume_fwd", False, _F32, False, None),
+    "cost_volume_bf16": _CvOp("mvs_cost_volume_fwd_bf16", False, torch.bfloat16, False, None),
+    "cost_volume_c4": _CvOp("mvs_cost_volume_fwd_c4", True, _F32, False, "cost_volume"),
+    "cost_volume_c4_absmax": _CvOp("mvs_cost_volume_fwd_c4_absmax", True, _F32, True, "cost_volume"),
+    "cost_volume_c4_split": _CvOp("mvs_cost_volume_fwd_c4_split", True, torch.int32, True, "cost_volume"),
+    "cost_volume_c4_bf16": _CvOp("mvs_cost_volume_fwd_c4_bf16", True, torch.bfloat16, False, "cost_volume"),
+}
+
+
+def _cv_forward(name, feat, K, R, T, d_min, d_int, batch_size, n_views, d_begin, d_count, d_scale):
+    """The body of the six fused warp + variance ops (_CV_OPS[name]).  Returns what the op does: (cv,
+    workspace) of the NCDHW ops (the backward reads the workspace), cv or (cv, bound words) of the quad ops."""
+    op = _CV_OPS[name]
+    lib, feat, cams = _cv_prelude(feat, K, R, T, d_min, d_int, batch_size, n_views)
+    n, c, h, w = feat.shape
+    if op.quad and c % 4:
+        raise ValueError("the channel-quad cost volume needs C % 4 == 0, got C=%d" % c)
+    cv = torch.empty(_cv_shape(batch_size, c, d_count, h, w, op.quad), device=feat.device, dtype=op.dtype)
+    absmax = torch.empty((8,), device=feat.device, dtype=torch.int32) if op.bound else None
+    ws = torch.empty((_ws_floats(batch_size, n_views, c, h, w, d_count),), device=feat.device, dtype=_F32)
+    tail = (() if op.kind is None else _events(op.kind)) + ((_lib.ptr(absmax),) if op.bound else ())
+    st = getattr(lib, op.entry)(_lib.ptr(feat), *[_lib.ptr(t) for t in cams], batch_size, n_views, c, h, w,
+                                d_begin, d_count, float(d_scale), _lib.ptr(ws), _lib.ptr(cv),
+                                _lib.stream_handle(feat.device), *tail)
+    _lib.check(st, op.entry)
+    if not op.quad:
+        return cv, ws
+    return (cv, absmax) if op.bound else cv
+
+
+def _cv_fake(name, feat, batch_size, n_views, d_count):
+    """_cv_forward's result as fake tensors."""
+    op = _CV_OPS[name]
+    n, c, h, w = feat.shape
+    cv = feat.new_empty(_cv_shape(batch_size, c, d_count, h, w, op.quad), dtype=op.dtype)
+    if not op.quad:
+        return cv, feat.new_empty((_ws_floats(batch_size, n_views, c, h, w, d_count),), dtype=_F32)
+    return (cv, feat.new_empty((8,), dtype=torch.int32)) if op.bound else cv
+
+
 @torch.library.custom_op("mvs::cost_volume", mutates_args=())
 def cost_volume(feat: torch.Tensor, K: torch.Tensor, R: torch.Tensor, T: torch.Tensor,
                 d_min: torch.Tensor, d_int: torch.Tensor, batch_size: int, n_views: int,
                 d_begin: int, d_count: int, d_scale: float) -> tuple[torch.Tensor, torch.Tensor]:
     """Fused warp + variance: returns (cv [B,C,d_count,h,w], workspace).  The workspace starts
     with the per-(image, plane) sampling matrices the backward reuses."""
-    _require_gpu(feat, "feature_maps")
-    lib = _lib.load()
-    feat = feat.to(_F32).contiguous()
-    K, R, T, d_min, d_int = _cams(K, R, T, d_min, d_int, feat.device, batch_size)
-    _check_geometry(feat, K, batch_size, n_views)
-    n, c, h, w = feat.shape
-    cv = torch.empty((batch_size, c, d_count, h, w), device=feat.device, dtype=_F32)
-    ws_bytes = lib.mvs_cost_volume_workspace_bytes(batch_size, n_views, c, h, w, d_count)
-    ws = torch.empty((max(ws_bytes, 4) // 4,), device=feat.device, dtype=_F32)
-    st = lib.mvs_cost_volume_fwd(_lib.ptr(feat), _lib.ptr(K), _lib.ptr(R), _lib.ptr(T),
-                                 _lib.ptr(d_min), _lib.ptr(d_int), batch_size, n_views, c, h, w,
-                                 d_begin, d_count, float(d_scale), _lib.ptr(ws), _lib.ptr(cv),
-                                 _lib.stream_handle(feat.device))
-    _lib.check(st, "mvs_cost_volume_fwd")
-    return cv, ws
-
-
-def _ws_floats(batch_size, n_views, c, h, w, d_count):
-    """Workspace size in floats, from the library's own size function (host-only, no GPU)."""
-    return max(_lib.load().mvs_cost_volume_workspace_bytes(batch_size, n_views, c, h, w, d_count), 4) // 4
+    return _cv_forward("cost_volume", feat, K, R, T, d_min, d_int, batch_size, n_views, d_begin, d_count,
+                       d_scale)
 
 
 @cost_volume.register_fake
 def _(feat, K, R, T, d_min, d_int, batch_size, n_views, d_begin, d_count, d_scale):
-    n, c, h, w = feat.shape
-    return (feat.new_empty((batch_size, c, d_count, h, w)),
-            feat.new_empty((_ws_floats(batch_size, n_views, c, h, w, d_count),)))
+    return _cv_fake("cost_volume", feat, batch_size, n_views, d_count)
 
 
 @torch.library.custom_op("mvs::cost_volume_bf16", mutates_args=())
@@ -108,32 +188,17 @@ def cost_volume_bf16(feat: torch.Tensor, K: torch.Tensor, R: torch.Tensor, T: to
                      d_begin: int, d_count: int, d_scale: float) -> tuple[torch.Tensor, torch.Tensor]:
     """mvs::cost_volume with a bf16 cost volume (SURVEY.md §8 f3, opt-in): the fp32 variance
     rounded to nearest-even in the kernel's store, half the HBM write."""
-    _require_gpu(feat, "feature_maps")
-    lib = _lib.load()
-    feat = feat.to(_F32).contiguous()
-    K, R, T, d_min, d_int = _cams(K, R, T, d_min, d_int, feat.device, batch_size)
-    _check_geometry(feat, K, batch_size, n_views)
-    n, c, h, w = feat.shape
-    cv = torch.empty((batch_size, c, d_count, h, w), device=feat.device, dtype=torch.bfloat16)
-    ws = torch.empty((_ws_floats(batch_size, n_views, c, h, w, d_count),), device=feat.device,
-                     dtype=_F32)
-    st = lib.mvs_cost_volume_fwd_bf16(_lib.ptr(feat), _lib.ptr(K), _lib.ptr(R), _lib.ptr(T),
-                                      _lib.ptr(d_min), _lib.ptr(d_int), batch_size, n_views, c, h, w,
-                                      d_begin, d_count, float(d_scale), _lib.ptr(ws), _lib.ptr(cv),
-                                      _lib.stream_handle(feat.device))
-    _lib.check(st, "mvs_cost_volume_fwd_bf16")
-    return cv, ws
+    return _cv_forward("cost_volume_bf16", feat, K, R, T, d_min, d_int, batch_size, n_views, d_begin, d_count,
+                       d_scale)
 
 
 @cost_volume_bf16.register_fake
 def _(feat, K, R, T, d_min, d_int, batch_size, n_views, d_begin, d_count, d_scale):
-    n, c, h, w = feat.shape
-    return (feat.new_empty((batch_size, c, d_count, h, w), dtype=torch.bfloat16),
-            feat.new_empty((_ws_floats(batch_size, n_views, c, h, w, d_count),)))
+    return _cv_fake("cost_volume_bf16", feat, batch_size, n_views, d_count)
 
 
-# Live timing of the main fused kernel inside a real step (bench.py): when set, a callable returning a
-# KERNEL_EVENT_HOOK(kind) -> (begin, end) pair of torch.cuda.Event for each fused-kernel call (kind
+# Live timing of the main fused kernel inside a real step (bench.py): when set, a callable kind ->
+# (begin, end) pair of torch.cuda.Event, asked for one pair per fused-kernel call (kind
 # "cost_volume": the cost_volume_c4* ops' warp kernel; "split_head": ops.split_head; "cv_head": the
 # opt-in fused head); the C ABI records them on the launch stream right around that kernel (the ops'
 # event arguments).
@@ -160,6 +225,14 @@ class timed_kernel:
         return False
 
 
+def _events(kind):
+    """KERNEL_EVENT_HOOK's event pair of one fused-kernel call as the C ABI's two event arguments, (None,
+    None) when no hook is set."""
+    if KERNEL_EVENT_HOOK is None:
+        return (None, None)
+    return tuple(ctypes.c_void_p(e.cuda_event) for e in KERNEL_EVENT_HOOK(kind))
+
+
 @torch.library.custom_op("mvs::cost_volume_c4", mutates_args=())
 def cost_volume_c4(feat: torch.Tensor, K: torch.Tensor, R: torch.Tensor, T: torch.Tensor,
                    d_min: torch.Tensor, d_int: torch.Tensor, batch_size: int, n_views: int,
@@ -167,32 +240,13 @@ def cost_volume_c4(feat: torch.Tensor, K: torch.Tensor, R: torch.Tensor, T: torc
     """mvs::cost_volume in the channel-quad layout cv[B][C/4][d_count][h][w][4] (the same values:
     cv_c4[b, q, d, y, x, j] == cv[b, 4q + j, d, y, x]), what conv3d_k3 / conv3d_region (CONV_S2)
     read with in_c4=True.  Inference only (no autograd formula), 2 <= n_views <= 8, C % 4 == 0."""
-    _require_gpu(feat, "feature_maps")
-    lib = _lib.load()
-    feat = feat.to(_F32).contiguous()
-    K, R, T, d_min, d_int = _cams(K, R, T, d_min, d_int, feat.device, batch_size)
-    _check_geometry(feat, K, batch_size, n_views)
-    n, c, h, w = feat.shape
-    if c % 4:
-        raise ValueError("the channel-quad cost volume needs C % 4 == 0, got C=%d" % c)
-    cv = torch.empty((batch_size, c // 4, d_count, h, w, 4), device=feat.device, dtype=_F32)
-    ws = torch.empty((_ws_floats(batch_size, n_views, c, h, w, d_count),), device=feat.device,
-                     dtype=_F32)
-    evs = (None, None)
-    if KERNEL_EVENT_HOOK is not None:
-        evs = tuple(ctypes.c_void_p(e.cuda_event) for e in KERNEL_EVENT_HOOK("cost_volume"))
-    st = lib.mvs_cost_volume_fwd_c4(_lib.ptr(feat), _lib.ptr(K), _lib.ptr(R), _lib.ptr(T),
-                                    _lib.ptr(d_min), _lib.ptr(d_int), batch_size, n_views, c, h, w,
-                                    d_begin, d_count, float(d_scale), _lib.ptr(ws), _lib.ptr(cv),
-                                    _lib.stream_handle(feat.device), *evs)
-    _lib.check(st, "mvs_cost_volume_fwd_c4")
-    return cv
+    return _cv_forward("cost_volume_c4", feat, K, R, T, d_min, d_int, batch_size, n_views, d_begin, d_count,
+                       d_scale)
 
 
 @cost_volume_c4.register_fake
 def _(feat, K, R, T, d_min, d_int, batch_size, n_views, d_begin, d_count, d_scale):
-    n, c, h, w = feat.shape
-    return feat.new_empty((batch_size, c // 4, d_count, h, w, 4))
+    return _cv_fake("cost_volume_c4", feat, batch_size, n_views, d_count)
 
 
 @torch.library.custom_op("mvs::cost_volume_c4_absmax", mutates_args=())
@@ -202,33 +256,13 @@ def cost_volume_c4_absmax(feat: torch.Tensor, K: torch.Tensor, R: torch.Tensor, 
     """cost_volume_c4 plus its bound words (mvs_cost_volume_fwd_c4_absmax): absmax int32[8] holds the
     per-XCD maxima of the |feat| bit patterns, every cost-volume element is <= (the largest, as a
     float)^2 -- what the split-fp16 conv_0_0 (conv3d_k3_split) scales its operands by."""
-    _require_gpu(feat, "feature_maps")
-    lib = _lib.load()
-    feat = feat.to(_F32).contiguous()
-    K, R, T, d_min, d_int = _cams(K, R, T, d_min, d_int, feat.device, batch_size)
-    _check_geometry(feat, K, batch_size, n_views)
-    n, c, h, w = feat.shape
-    if c % 4:
-        raise ValueError("the channel-quad cost volume needs C % 4 == 0, got C=%d" % c)
-    cv = torch.empty((batch_size, c // 4, d_count, h, w, 4), device=feat.device, dtype=_F32)
-    absmax = torch.empty((8,), device=feat.device, dtype=torch.int32)
-    ws = torch.empty((_ws_floats(batch_size, n_views, c, h, w, d_count),), device=feat.device,
-                     dtype=_F32)
-    evs = (None, None)
-    if KERNEL_EVENT_HOOK is not None:
-        evs = tuple(ctypes.c_void_p(e.cuda_event) for e in KERNEL_EVENT_HOOK("cost_volume"))
-    st = lib.mvs_cost_volume_fwd_c4_absmax(_lib.ptr(feat), _lib.ptr(K), _lib.ptr(R), _lib.ptr(T),
-                                           _lib.ptr(d_min), _lib.ptr(d_int), batch_size, n_views, c, h, w,
-                                           d_begin, d_count, float(d_scale), _lib.ptr(ws), _lib.ptr(cv),
-                                           _lib.stream_handle(feat.device), *evs, _lib.ptr(absmax))
-    _lib.check(st, "mvs_cost_volume_fwd_c4_absmax")
-    return cv, absmax
+    return _cv_forward("cost_volume_c4_absmax", feat, K, R, T, d_min, d_int, batch_size, n_views, d_begin, d_count,
+                       d_scale)
 
 
 @cost_volume_c4_absmax.register_fake
 def _(feat, K, R, T, d_min, d_int, batch_size, n_views, d_begin, d_count, d_scale):
-    n, c, h, w = feat.shape
-    return feat.new_empty((batch_size, c // 4, d_count, h, w, 4)), feat.new_empty((8,), dtype=torch.int32)
+    return _cv_fake("cost_volume_c4_absmax", feat, batch_size, n_views, d_count)
 
 
 @torch.library.custom_op("mvs::cost_volume_c4_split", mutates_args=())
@@ -239,34 +273,13 @@ def cost_volume_c4_split(feat: torch.Tensor, K: torch.Tensor, R: torch.Tensor, T
     holding, per 16-byte element, the fp16 hi / lo parts of 4 variances scaled by 2^e (e from the bound
     words, returned beside it) -- the operands the split-fp16 regulariser kernels read without
     converting.  unsplit_cost_volume() gives the fp32 values back (to 2^-22)."""
-    _require_gpu(feat, "feature_maps")
-    lib = _lib.load()
-    feat = feat.to(_F32).contiguous()
-    K, R, T, d_min, d_int = _cams(K, R, T, d_min, d_int, feat.device, batch_size)
-    _check_geometry(feat, K, batch_size, n_views)
-    n, c, h, w = feat.shape
-    if c % 4:
-        raise ValueError("the channel-quad cost volume needs C % 4 == 0, got C=%d" % c)
-    cv = torch.empty((batch_size, c // 4, d_count, h, w, 4), device=feat.device, dtype=torch.int32)
-    absmax = torch.empty((8,), device=feat.device, dtype=torch.int32)
-    ws = torch.empty((_ws_floats(batch_size, n_views, c, h, w, d_count),), device=feat.device,
-                     dtype=_F32)
-    evs = (None, None)
-    if KERNEL_EVENT_HOOK is not None:
-        evs = tuple(ctypes.c_void_p(e.cuda_event) for e in KERNEL_EVENT_HOOK("cost_volume"))
-    st = lib.mvs_cost_volume_fwd_c4_split(_lib.ptr(feat), _lib.ptr(K), _lib.ptr(R), _lib.ptr(T),
-                                          _lib.ptr(d_min), _lib.ptr(d_int), batch_size, n_views, c, h, w,
-                                          d_begin, d_count, float(d_scale), _lib.ptr(ws), _lib.ptr(cv),
-                                          _lib.stream_handle(feat.device), *evs, _lib.ptr(absmax))
-    _lib.check(st, "mvs_cost_volume_fwd_c4_split")
-    return cv, absmax
+    return _cv_forward("cost_volume_c4_split", feat, K, R, T, d_min, d_int, batch_size, n_views, d_begin, d_count,
+                       d_scale)
 
 
 @cost_volume_c4_split.register_fake
 def _(feat, K, R, T, d_min, d_int, batch_size, n_views, d_begin, d_count, d_scale):
-    n, c, h, w = feat.shape
-    return (feat.new_empty((batch_size, c // 4, d_count, h, w, 4), dtype=torch.int32),
-            feat.new_empty((8,), dtype=torch.int32))
+    return _cv_fake("cost_volume_c4_split", feat, batch_size, n_views, d_count)
 
 
 def split_exponent(absmax):
@@ -361,25 +374,15 @@ def cost_volume_head(feat: torch.Tensor, K: torch.Tensor, R: torch.Tensor, T: to
     volume on the box [scv_lo, scv_hi) only (what conv_2_0 / conv_3_0 read), int32
     [B, 8, *(scv_hi - scv_lo), 4]; absmax its bound words.  Bit-identical to cost_volume_c4_split -> conv3d_k3_split /
     conv_s2_split.  C = 32, 2 <= n_views <= 3, d_count even, pad odd; inference only."""
-    _require_gpu(feat, "feature_maps")
-    lib = _lib.load()
-    feat = feat.to(_F32).contiguous()
-    K, R, T, d_min, d_int = _cams(K, R, T, d_min, d_int, feat.device, batch_size)
-    _check_geometry(feat, K, batch_size, n_views)
+    lib, feat, cams = _cv_prelude(feat, K, R, T, d_min, d_int, batch_size, n_views)
     n, c, h, w = feat.shape
     if tuple(w0.shape) != (8, 32, 3, 3, 3) or tuple(w1.shape) != (16, 32, 3, 3, 3):
         raise ValueError("conv_0_0 [8, 32, 3, 3, 3] and conv_1_0 [16, 32, 3, 3, 3] weights expected")
     dev = feat.device
     f0, e0 = derived("k3split", (w0,), lambda wt: split_weight_fragments(wt, dev), dev)
     f1, e1 = derived("s2split", (w1,), lambda wt: _s2_split_fragments(wt, dev), dev)
-
-    def bn(ts):
-        ts = [t if t is None else t.to(device=dev, dtype=_F32).contiguous() for t in ts]
-        if any(t is None for t in ts) and not all(t is None for t in ts):
-            raise ValueError("BN scale, shift and mean go together")
-        return ts, [None if t is None else _lib.ptr(t) for t in ts]
-    bn0, bp0 = bn((bn0_scale, bn0_shift, bn0_mean))
-    bn1, bp1 = bn((bn1_scale, bn1_shift, bn1_mean))
+    bn0, bp0 = _bn_triple(bn0_scale, bn0_shift, bn0_mean, dev)
+    bn1, bp1 = _bn_triple(bn1_scale, bn1_shift, bn1_mean, dev)
     y0 = torch.empty((batch_size, 8, d_count, h, w), device=dev, dtype=_F32)
     y1 = torch.empty([batch_size] + [int(v) for v in y1_size] + [16], device=dev, dtype=_F32)
     boxed = all(int(hi_) > int(lo_) for lo_, hi_ in zip(scv_lo, scv_hi))
@@ -387,15 +390,11 @@ def cost_volume_head(feat: torch.Tensor, K: torch.Tensor, R: torch.Tensor, T: to
     scv = torch.empty([batch_size, 8] + box + [4] if boxed else [0], device=dev, dtype=torch.int32)
     absmax = torch.empty((8,), device=dev, dtype=torch.int32)
     ws = torch.empty((_ws_floats(batch_size, n_views, c, h, w, d_count),), device=dev, dtype=_F32)
-    evs = (None, None)
-    if KERNEL_EVENT_HOOK is not None:
-        evs = tuple(ctypes.c_void_p(e.cuda_event) for e in KERNEL_EVENT_HOOK("cv_head"))
-    st = lib.mvs_cost_volume_head_fwd(_lib.ptr(feat), _lib.ptr(K), _lib.ptr(R), _lib.ptr(T), _lib.ptr(d_min),
-                                      _lib.ptr(d_int), batch_size, n_views, c, h, w, d_begin, d_count,
-                                      float(d_scale), _lib.ptr(f0), int(e0), *bp0, _lib.ptr(f1), int(e1), *bp1,
-                                      _ints3(pad), _ints3(y1_origin), _ints3(y1_size), _ints3(scv_lo),
+    st = lib.mvs_cost_volume_head_fwd(_lib.ptr(feat), *[_lib.ptr(t) for t in cams], batch_size, n_views, c, h, w,
+                                      d_begin, d_count, float(d_scale), _lib.ptr(f0), int(e0), *bp0, _lib.ptr(f1),
+                                      int(e1), *bp1, _ints3(pad), _ints3(y1_origin), _ints3(y1_size), _ints3(scv_lo),
                                       _ints3(scv_hi), _lib.ptr(ws), _lib.ptr(absmax), _lib.ptr(y0), _lib.ptr(y1),
-                                      _lib.ptr(scv) if boxed else None, _lib.stream_handle(dev), *evs)
+                                      _lib.ptr(scv) if boxed else None, _lib.stream_handle(dev), *_events("cv_head"))
     _lib.check(st, "mvs_cost_volume_head_fwd")
     return y0, y1, scv, absmax
 
@@ -435,23 +434,14 @@ def split_head(scv: torch.Tensor, absmax: torch.Tensor, w0: torch.Tensor, bn0_sc
     dev = scv.device
     f0, e0 = derived("k3split", (w0,), lambda wt: split_weight_fragments(wt, dev), dev)
     f1, e1 = derived("s2split", (w1,), lambda wt: _s2_split_fragments(wt, dev), dev)
-
-    def bn(ts):
-        ts = [t if t is None else t.to(device=dev, dtype=_F32).contiguous() for t in ts]
-        if any(t is None for t in ts) and not all(t is None for t in ts):
-            raise ValueError("BN scale, shift and mean go together")
-        return ts, [None if t is None else _lib.ptr(t) for t in ts]
-    bn0, bp0 = bn((bn0_scale, bn0_shift, bn0_mean))
-    bn1, bp1 = bn((bn1_scale, bn1_shift, bn1_mean))
+    bn0, bp0 = _bn_triple(bn0_scale, bn0_shift, bn0_mean, dev)
+    bn1, bp1 = _bn_triple(bn1_scale, bn1_shift, bn1_mean, dev)
     y0 = torch.empty((b, 8, d, h, w), device=dev, dtype=_F32)
     y1 = torch.empty([b] + [int(v) for v in y1_size] + [16], device=dev, dtype=_F32)
-    evs = (None, None)
-    if KERNEL_EVENT_HOOK is not None:
-        evs = tuple(ctypes.c_void_p(e.cuda_event) for e in KERNEL_EVENT_HOOK("split_head"))
     st = lib.mvs_split_head_fwd(_lib.ptr(scv), _lib.ptr(absmax.contiguous()), b, d, h, w, _lib.ptr(f0), int(e0),
                                 *bp0, _lib.ptr(f1), int(e1), *bp1, _ints3(pad), _ints3(y1_origin),
                                 _ints3(y1_size), _lib.ptr(y0), _lib.ptr(y1), _bound_ptr(y1_bound),
-                                _lib.stream_handle(dev), *evs)
+                                _lib.stream_handle(dev), *_events("split_head"))
     _lib.check(st, "mvs_split_head_fwd")
     return y0, y1
 
@@ -472,32 +462,13 @@ def cost_volume_c4_bf16(feat: torch.Tensor, K: torch.Tensor, R: torch.Tensor, T:
     layout [B, C/4, d_count, h, w, 4], each value the fp32 variance rounded to nearest-even (equal to
     cost_volume_c4(...).to(torch.bfloat16)); half the HBM write, and conv3d_k3 / conv3d_region (S2)
     read it widened to fp32.  Inference only, 2 <= n_views <= 8, C % 4 == 0."""
-    _require_gpu(feat, "feature_maps")
-    lib = _lib.load()
-    feat = feat.to(_F32).contiguous()
-    K, R, T, d_min, d_int = _cams(K, R, T, d_min, d_int, feat.device, batch_size)
-    _check_geometry(feat, K, batch_size, n_views)
-    n, c, h, w = feat.shape
-    if c % 4:
-        raise ValueError("the channel-quad cost volume needs C % 4 == 0, got C=%d" % c)
-    cv = torch.empty((batch_size, c // 4, d_count, h, w, 4), device=feat.device, dtype=torch.bfloat16)
-    ws = torch.empty((_ws_floats(batch_size, n_views, c, h, w, d_count),), device=feat.device,
-                     dtype=_F32)
-    evs = (None, None)
-    if KERNEL_EVENT_HOOK is not None:
-        evs = tuple(ctypes.c_void_p(e.cuda_event) for e in KERNEL_EVENT_HOOK("cost_volume"))
-    st = lib.mvs_cost_volume_fwd_c4_bf16(_lib.ptr(feat), _lib.ptr(K), _lib.ptr(R), _lib.ptr(T),
-                                         _lib.ptr(d_min), _lib.ptr(d_int), batch_size, n_views, c, h, w,
-                                         d_begin, d_count, float(d_scale), _lib.ptr(ws), _lib.ptr(cv),
-                                         _lib.stream_handle(feat.device), *evs)
-    _lib.check(st, "mvs_cost_volume_fwd_c4_bf16")
-    return cv
+    return _cv_forward("cost_volume_c4_bf16", feat, K, R, T, d_min, d_int, batch_size, n_views, d_begin, d_count,
+                       d_scale)
 
 
 @cost_volume_c4_bf16.register_fake
 def _(feat, K, R, T, d_min, d_int, batch_size, n_views, d_begin, d_count, d_scale):
-    n, c, h, w = feat.shape
-    return feat.new_empty((batch_size, c // 4, d_count, h, w, 4), dtype=torch.bfloat16)
+    return _cv_fake("cost_volume_c4_bf16", feat, batch_size, n_views, d_count)
 
 
 @torch.library.custom_op("mvs::cost_volume_backward", mutates_args=())
@@ -559,18 +530,13 @@ def homography_warp(feat: torch.Tensor, K: torch.Tensor, R: torch.Tensor, T: tor
                     d_min: torch.Tensor, d_int: torch.Tensor, batch_size: int, n_views: int,
                     d_begin: int, d_count: int, d_scale: float) -> torch.Tensor:
     """warped [B*V, C, d_count, h, w] (homography.py:6-92 output layout)."""
-    _require_gpu(feat, "feature_maps")
-    lib = _lib.load()
-    feat = feat.to(_F32).contiguous()
-    K, R, T, d_min, d_int = _cams(K, R, T, d_min, d_int, feat.device, batch_size)
-    _check_geometry(feat, K, batch_size, n_views)
+    lib, feat, cams = _cv_prelude(feat, K, R, T, d_min, d_int, batch_size, n_views)
     n, c, h, w = feat.shape
     warped = torch.empty((n, c, d_count, h, w), device=feat.device, dtype=_F32)
     ws = torch.empty((n * d_count * 9,), device=feat.device, dtype=_F32)
-    st = lib.mvs_homography_warp_fwd(_lib.ptr(feat), _lib.ptr(K), _lib.ptr(R), _lib.ptr(T),
-                                     _lib.ptr(d_min), _lib.ptr(d_int), batch_size, n_views, c, h,
-                                     w, d_begin, d_count, float(d_scale), _lib.ptr(ws),
-                                     _lib.ptr(warped), _lib.stream_handle(feat.device))
+    st = lib.mvs_homography_warp_fwd(_lib.ptr(feat), *[_lib.ptr(t) for t in cams], batch_size, n_views, c, h, w,
+                                     d_begin, d_count, float(d_scale), _lib.ptr(ws), _lib.ptr(warped),
+                                     _lib.stream_handle(feat.device))
     _lib.check(st, "mvs_homography_warp_fwd")
     return warped
 
@@ -723,10 +689,7 @@ def conv3d_k3(x: torch.Tensor, weight: torch.Tensor, bn_scale: Optional[torch.Te
     else:
         w = derived("k3", (weight,), lambda wt: wt.to(device=x.device, dtype=_F32).permute(1, 2, 3, 4, 0).contiguous(),
                     x.device)
-    bn = [t if t is None else t.to(device=x.device, dtype=_F32).contiguous() for t in (bn_scale, bn_shift, bn_mean)]
-    if any(t is None for t in bn) and not all(t is None for t in bn):
-        raise ValueError("bn_scale, bn_shift and bn_mean go together")
-    bp = [None if t is None else _lib.ptr(t) for t in bn]
+    bn, bp = _bn_triple(bn_scale, bn_shift, bn_mean, x.device)
     y = torch.empty((b, cout, d, h, wd), device=x.device, dtype=_F32)
     flags = ((_lib.MVS_CONV_IN_C4 if in_c4 else 0) | (_lib.MVS_CONV_WINO_Z if wino_z else 0)
              | (_lib.MVS_CONV_IN_BF16 if quad_bf16 else 0))
@@ -738,8 +701,8 @@ def conv3d_k3(x: torch.Tensor, weight: torch.Tensor, bn_scale: Optional[torch.Te
         x2 = x2.to(_F32).contiguous()
         in_bn = in_bn.to(device=x.device, dtype=_F32).contiguous()
     st = lib.mvs_conv3d_k3_fwd(_lib.ptr(x), flags, _lib.ptr(w), _lib.ptr(y),
-                               b, cin, cout, d, h, wd, *bp, None if x2 is None else _lib.ptr(x2),
-                               None if in_bn is None else _lib.ptr(in_bn), _lib.stream_handle(x.device))
+                               b, cin, cout, d, h, wd, *bp, _opt_ptr(x2), _opt_ptr(in_bn),
+                               _lib.stream_handle(x.device))
     _lib.check(st, "mvs_conv3d_k3_fwd")
     return y
 
@@ -795,18 +758,14 @@ def conv_head_fp32(cv4: torch.Tensor, w0: torch.Tensor, bn0_scale: Optional[torc
     w1r = derived("head1_region", (w1,), lambda wt: wt.detach().to(device=dev, dtype=_F32).permute(2, 3, 4, 0, 1)
                   .reshape(27, 16, 32).contiguous(), dev)
     w1p = derived("head1_pass", (w1,), lambda wt: w1r.view(27, 16, 8, 4).permute(2, 0, 1, 3).contiguous(), dev)
-    bns = []
-    for t in (bn0_scale, bn0_shift, bn0_mean, bn1_scale, bn1_shift, bn1_mean):
-        bns.append(None if t is None else t.to(device=dev, dtype=_F32).contiguous())
+    bn0, bp0 = _bn_triple(bn0_scale, bn0_shift, bn0_mean, dev)
+    bn1, bp1 = _bn_triple(bn1_scale, bn1_shift, bn1_mean, dev)
     y0 = torch.empty((b, 8, d, h, wd), device=dev, dtype=_F32)
     y1 = torch.empty([b] + [int(v) for v in y1_size] + [16], device=dev, dtype=_F32)
-    bp = [None if t is None else _lib.ptr(t) for t in bns]
-    evs = (None, None)
-    if KERNEL_EVENT_HOOK is not None:   # around the fused kernel (bench.py's fp32 roofline kernel)
-        evs = tuple(ctypes.c_void_p(e.cuda_event) for e in KERNEL_EVENT_HOOK("conv_head"))
-    st = lib.mvs_conv_head_fp32_fwd(_lib.ptr(cv4), b, d, h, wd, _lib.ptr(w0z), *bp[:3], _lib.ptr(w1r), _lib.ptr(w1p),
-                                    *bp[3:], _ints3(pad), _ints3(y1_origin), _ints3(y1_size), _lib.ptr(y0), _lib.ptr(y1),
-                                    _lib.stream_handle(dev), *evs)
+    # the events go around the fused kernel (bench.py's fp32 roofline kernel)
+    st = lib.mvs_conv_head_fp32_fwd(_lib.ptr(cv4), b, d, h, wd, _lib.ptr(w0z), *bp0, _lib.ptr(w1r), _lib.ptr(w1p),
+                                    *bp1, _ints3(pad), _ints3(y1_origin), _ints3(y1_size), _lib.ptr(y0), _lib.ptr(y1),
+                                    _lib.stream_handle(dev), *_events("conv_head"))
     _lib.check(st, "mvs_conv_head_fp32_fwd")
     return y0, y1
 
@@ -840,18 +799,14 @@ def conv3d_k3_split(x: torch.Tensor, absmax: Optional[torch.Tensor], weight: tor
     x = x.contiguous()
     b, _, d, h, wd, _ = x.shape
     frag, wexp = derived("k3split", (weight,), lambda wt: split_weight_fragments(wt, x.device), x.device)
-    bn = [t if t is None else t.to(device=x.device, dtype=_F32).contiguous() for t in (bn_scale, bn_shift, bn_mean)]
-    if any(t is None for t in bn) and not all(t is None for t in bn):
-        raise ValueError("bn_scale, bn_shift and bn_mean go together")
-    bp = [None if t is None else _lib.ptr(t) for t in bn]
+    bn, bp = _bn_triple(bn_scale, bn_shift, bn_mean, x.device)
     if absmax is not None:
         if absmax.numel() != 8 or absmax.dtype != torch.int32 or absmax.device != x.device:
             raise ValueError("absmax: int32[8] on the volume's device expected")
         absmax = absmax.contiguous()
     y = torch.empty((b, 8, d, h, wd), device=x.device, dtype=_F32)
     st = lib.mvs_conv3d_k3_split_fwd(_lib.ptr(x), _lib.MVS_CONV_IN_SPLIT if split_in else 0, _lib.ptr(frag), int(wexp),
-                                     None if absmax is None else _lib.ptr(absmax), _lib.ptr(y),
-                                     b, d, h, wd, *bp, _lib.stream_handle(x.device))
+                                     _opt_ptr(absmax), _lib.ptr(y), b, d, h, wd, *bp, _lib.stream_handle(x.device))
     _lib.check(st, "mvs_conv3d_k3_split_fwd")
     return y
 
@@ -884,19 +839,15 @@ def conv_s2_split(x: torch.Tensor, absmax: Optional[torch.Tensor], weight: torch
         raise ValueError("dims %s do not match the volume %s" % (list(dims), list(x.shape[2:5])))
     x = x.contiguous()
     frag, wexp = derived("s2split", (weight,), lambda wt: _s2_split_fragments(wt, x.device), x.device)
-    bn = [t if t is None else t.to(device=x.device, dtype=_F32).contiguous() for t in (bn_scale, bn_shift, bn_mean)]
-    if any(t is None for t in bn) and not all(t is None for t in bn):
-        raise ValueError("bn_scale, bn_shift and bn_mean go together")
-    bp = [None if t is None else _lib.ptr(t) for t in bn]
+    bn, bp = _bn_triple(bn_scale, bn_shift, bn_mean, x.device)
     if absmax is not None:
         if absmax.numel() != 8 or absmax.dtype != torch.int32 or absmax.device != x.device:
             raise ValueError("absmax: int32[8] on the volume's device expected")
         absmax = absmax.contiguous()
     y = torch.empty([x.shape[0]] + [int(v) for v in out_size] + [16], device=x.device, dtype=_F32)
     st = lib.mvs_conv3d_s2_split_fwd(_lib.ptr(x), _lib.MVS_CONV_IN_SPLIT if split_in else 0, _lib.ptr(frag), int(wexp),
-                                     None if absmax is None else _lib.ptr(absmax), _lib.ptr(y), x.shape[0],
-                                     _ints3(dims), _ints3(out_origin), _ints3(out_size), _ints3(pad), *bp,
-                                     _lib.stream_handle(x.device))
+                                     _opt_ptr(absmax), _lib.ptr(y), x.shape[0], _ints3(dims), _ints3(out_origin),
+                                     _ints3(out_size), _ints3(pad), *bp, _lib.stream_handle(x.device))
     _lib.check(st, "mvs_conv3d_s2_split_fwd")
     return y
 
@@ -907,25 +858,13 @@ def _(x, absmax, weight, dims, out_origin, out_size, pad, bn_scale=None, bn_shif
 
 
 def _s2_split_fragments(weight, device):
-    lib = _lib.load()
-    w = weight.detach().to(device="cpu", dtype=_F32).contiguous()
-    frag = torch.empty((27 * 2 * 64 * 8,), dtype=torch.int16)
-    e = ctypes.c_int(0)
-    st = lib.mvs_conv3d_s2_split_weights(_lib.ptr(w), _lib.ptr(frag), ctypes.byref(e))
-    _lib.check(st, "mvs_conv3d_s2_split_weights")
-    return frag.to(device), e.value
+    return _host_fragments("mvs_conv3d_s2_split_weights", weight, 27 * 2 * 64 * 8, device=device)
 
 
 def split_weight_fragments(weight, device):
     """(fp16 MFMA fragments [27*64*8] int16 on ``device``, exponent) of conv_0_0's weight, formed on
     the host by mvs_conv3d_split_weights (the C ABI's own split, so every caller gets the same)."""
-    lib = _lib.load()
-    w = weight.detach().to(device="cpu", dtype=_F32).contiguous()
-    frag = torch.empty((27 * 64 * 8,), dtype=torch.int16)
-    e = ctypes.c_int(0)
-    st = lib.mvs_conv3d_split_weights(_lib.ptr(w), _lib.ptr(frag), ctypes.byref(e))
-    _lib.check(st, "mvs_conv3d_split_weights")
-    return frag.to(device), e.value
+    return _host_fragments("mvs_conv3d_split_weights", weight, 27 * 64 * 8, device=device)
 
 
 def _wino_z_weight(wt):
@@ -960,6 +899,11 @@ def conv2d_supported(conv):
             and (conv.in_channels, conv.out_channels, k, conv.stride[0]) in CONV2D_SHAPES)
 
 
+def _conv2d_out(n, k, stride):
+    """Output length of a conv2d dimension of length n (kernel k, padding k // 2)."""
+    return (n + 2 * (k // 2) - k) // stride + 1
+
+
 # (y_bound is raised in place; not declared as a mutation, as conv3d_region_split's bound words)
 @torch.library.custom_op("mvs::conv2d", mutates_args=())
 def conv2d(x: torch.Tensor, weight: torch.Tensor, stride: int, bn_scale: Optional[torch.Tensor] = None,
@@ -981,11 +925,8 @@ def conv2d(x: torch.Tensor, weight: torch.Tensor, stride: int, bn_scale: Optiona
     # the kernel reads weight[c_in][k][k][c_out] (pairs of output channels per 8-byte scalar load)
     w = derived("conv2d", (weight,), lambda wt: wt.to(device=x.device, dtype=_F32).permute(1, 2, 3, 0).contiguous(),
                 x.device)
-    bn = [t if t is None else t.to(device=x.device, dtype=_F32).contiguous() for t in (bn_scale, bn_shift, bn_mean)]
-    if any(t is None for t in bn) and not all(t is None for t in bn):
-        raise ValueError("bn_scale, bn_shift and bn_mean go together")
-    bp = [None if t is None else _lib.ptr(t) for t in bn]
-    ho, wo = (h + 2 * (k // 2) - k) // stride + 1, (wd + 2 * (k // 2) - k) // stride + 1
+    bn, bp = _bn_triple(bn_scale, bn_shift, bn_mean, x.device)
+    ho, wo = _conv2d_out(h, k, stride), _conv2d_out(wd, k, stride)
     y = torch.empty((n, cout, ho, wo), device=x.device, dtype=_F32)
     st = lib.mvs_conv2d_fwd(_lib.ptr(x), _lib.ptr(w), _lib.ptr(y), n, cin, cout, h, wd, k, stride, *bp,
                             _bound_ptr(y_bound), _lib.stream_handle(x.device))
@@ -997,8 +938,8 @@ def conv2d(x: torch.Tensor, weight: torch.Tensor, stride: int, bn_scale: Optiona
 def _(x, weight, stride, bn_scale=None, bn_shift=None, bn_mean=None, y_bound=None):
     _eager_only("conv2d", y_bound=y_bound)
     k = weight.shape[2]
-    return x.new_empty((x.shape[0], weight.shape[0], (x.shape[2] + 2 * (k // 2) - k) // stride + 1,
-                        (x.shape[3] + 2 * (k // 2) - k) // stride + 1))
+    return x.new_empty((x.shape[0], weight.shape[0], _conv2d_out(x.shape[2], k, stride),
+                        _conv2d_out(x.shape[3], k, stride)))
 
 
 # (c_in, c_out, k, stride) of the split-fp16 MFMA kernel (csrc/conv2d_split.hip): the encoder's layers
@@ -1009,16 +950,10 @@ CONV2D_SPLIT_SHAPES = frozenset({(8, 8, 3, 1), (8, 16, 5, 2), (16, 16, 3, 1), (1
 def conv2d_split_fragments(weight, device):
     """(split-fp16 MFMA fragments on ``device``, exponent) of an nn.Conv2d weight [c_out][c_in][k][k],
     formed on the host by mvs_conv2d_split_weights."""
-    lib = _lib.load()
-    w = weight.detach().to(device="cpu", dtype=_F32).contiguous()
-    cout, cin, k, _ = w.shape
+    cout, cin, k, _ = weight.shape
     kb = -(-(k * k) // (32 // cin))
     parts = 1 if cout == 8 else 2 * (cout // 16)
-    frag = torch.empty((kb * parts * 64 * 8,), dtype=torch.int16)
-    e = ctypes.c_int(0)
-    st = lib.mvs_conv2d_split_weights(_lib.ptr(w), cin, cout, k, _lib.ptr(frag), ctypes.byref(e))
-    _lib.check(st, "mvs_conv2d_split_weights")
-    return frag.to(device), e.value
+    return _host_fragments("mvs_conv2d_split_weights", weight, kb * parts * 64 * 8, cin, cout, k, device=device)
 
 
 # (y_bound is raised in place; not declared as a mutation, as conv3d_region_split's bound words)
@@ -1043,11 +978,8 @@ def conv2d_split(x: torch.Tensor, weight: torch.Tensor, stride: int, x_bound: to
     x = x.to(_F32).contiguous()
     dev = x.device
     frag, ew = derived("conv2d_split", (weight,), lambda wt: conv2d_split_fragments(wt, dev), dev)
-    bn = [t if t is None else t.to(device=dev, dtype=_F32).contiguous() for t in (bn_scale, bn_shift, bn_mean)]
-    if any(t is None for t in bn) and not all(t is None for t in bn):
-        raise ValueError("bn_scale, bn_shift and bn_mean go together")
-    bp = [None if t is None else _lib.ptr(t) for t in bn]
-    ho, wo = (h + 2 * (k // 2) - k) // stride + 1, (wd + 2 * (k // 2) - k) // stride + 1
+    bn, bp = _bn_triple(bn_scale, bn_shift, bn_mean, dev)
+    ho, wo = _conv2d_out(h, k, stride), _conv2d_out(wd, k, stride)
     y = torch.empty((n, cout, ho, wo), device=dev, dtype=_F32)
     st = lib.mvs_conv2d_split_fwd(_lib.ptr(x), _lib.ptr(frag), ew, _lib.ptr(y), n, cin, cout, h, wd, k, stride,
                                   *bp, _bound_ptr(x_bound), _bound_ptr(y_bound), _lib.stream_handle(dev))
@@ -1059,8 +991,8 @@ def conv2d_split(x: torch.Tensor, weight: torch.Tensor, stride: int, x_bound: to
 def _(x, weight, stride, x_bound, y_bound=None, bn_scale=None, bn_shift=None, bn_mean=None):
     _eager_only("conv2d_split", y_bound=y_bound)
     k = weight.shape[2]
-    return x.new_empty((x.shape[0], weight.shape[0], (x.shape[2] + 2 * (k // 2) - k) // stride + 1,
-                        (x.shape[3] + 2 * (k // 2) - k) // stride + 1))
+    return x.new_empty((x.shape[0], weight.shape[0], _conv2d_out(x.shape[2], k, stride),
+                        _conv2d_out(x.shape[3], k, stride)))
 
 
 # ----------------------------------------------------------------------------------------------
@@ -1094,17 +1026,13 @@ def deconv3d_k3s2(x: torch.Tensor, origin: list[int], weight: torch.Tensor, out_
                 x.device)
     flags = _lib.MVS_DECONV_WEIGHT_TAPS | (_lib.MVS_LAYOUT_CHANNELS_LAST if channels_last else 0)
     d, h, wd = out_dims
-    f = lambda t: None if t is None else t.to(device=x.device, dtype=_F32).contiguous()
-    sc, sh, mu, res = f(bn_scale), f(bn_shift), f(bn_mean), f(residual)
-    if (sc is None) != (sh is None) or (sc is None) != (mu is None):
-        raise ValueError("bn_scale, bn_shift and bn_mean go together")
+    bn, bp = _bn_triple(bn_scale, bn_shift, bn_mean, x.device)
+    res = residual if residual is None else residual.to(device=x.device, dtype=_F32).contiguous()
     if res is not None and tuple(res.shape) != (b, 8, d, h, wd):
         raise ValueError("residual must be [B, 8, D, H, W]")
     y = torch.empty((b, 8, d, h, wd), device=x.device, dtype=_F32)
-    pt = lambda t: None if t is None else _lib.ptr(t)
-    st = lib.mvs_deconv3d_k3s2_fwd(_lib.ptr(x), pt(x2), flags, b, cin, 8, rd, rh,
-                                   rw, *origin, _lib.ptr(w), d, h, wd, *pad, pt(sc), pt(sh), pt(mu), pt(res),
-                                   _lib.ptr(y), _lib.stream_handle(x.device))
+    st = lib.mvs_deconv3d_k3s2_fwd(_lib.ptr(x), _opt_ptr(x2), flags, b, cin, 8, rd, rh, rw, *origin, _lib.ptr(w),
+                                   d, h, wd, *pad, *bp, _opt_ptr(res), _lib.ptr(y), _lib.stream_handle(x.device))
     _lib.check(st, "mvs_deconv3d_k3s2_fwd")
     return y
 
@@ -1174,10 +1102,6 @@ def region_weight(module):
                    lambda w: w.permute(2, 3, 4, 0, 1).reshape(27, w.shape[0], w.shape[1]).contiguous())
 
 
-def _ints3(v):
-    return (ctypes.c_int * 3)(*[int(a) for a in v])
-
-
 # (the bound words are raised in place; not declared as a mutation: torch's ADInplaceOrView wrapper
 # indexes every declared mutable argument positionally, which fails for an omitted trailing default)
 @torch.library.custom_op("mvs::conv3d_region", mutates_args=())
@@ -1210,20 +1134,15 @@ def conv3d_region(x: torch.Tensor, x2: Optional[torch.Tensor], weight: torch.Ten
     w = weight.to(device=x.device, dtype=_F32).contiguous()
     _, cout, cin = w.shape
     b = x.shape[0]
-    bn = [t if t is None else t.to(device=x.device, dtype=_F32).contiguous() for t in (bn_scale, bn_shift, bn_mean)]
-    if any(t is None for t in bn) and not all(t is None for t in bn):
-        raise ValueError("bn_scale, bn_shift and bn_mean go together")
+    bn, bp = _bn_triple(bn_scale, bn_shift, bn_mean, x.device)
     shape = (b, cout) + tuple(out_size) if out_ncdhw else (b,) + tuple(out_size) + (cout,)
     y = torch.empty(shape, device=x.device, dtype=_F32)
     flags = ((_lib.MVS_CONV_OUT_NCDHW if out_ncdhw else 0) | (_lib.MVS_CONV_IN_C4 if in_c4 else 0)
              | (_lib.MVS_CONV_IN_BF16 if quad_bf16 else 0) | (_lib.MVS_CONV_IN_SPLIT if quad_split else 0)
              | (_lib.MVS_CONV_PER_LANE if per_lane else 0) | (_lib.MVS_CONV_S2_LDS if s2_lds else 0))
-    st = lib.mvs_conv3d_region_fwd(int(mode), flags, _lib.ptr(x), None if x2 is None else _lib.ptr(x2), _lib.ptr(w),
+    st = lib.mvs_conv3d_region_fwd(int(mode), flags, _lib.ptr(x), _opt_ptr(x2), _lib.ptr(w),
                                    _lib.ptr(y), b, cin, cout, _ints3(dims), _ints3(out_origin), _ints3(out_size),
-                                   None if in_origin is None else _ints3(in_origin),
-                                   None if in_size is None else _ints3(in_size),
-                                   None if pad is None else _ints3(pad),
-                                   *[None if t is None else _lib.ptr(t) for t in bn],
+                                   _opt_ints3(in_origin), _opt_ints3(in_size), _opt_ints3(pad), *bp,
                                    _lib.ptr(absmax.contiguous()) if quad_split else None,
                                    _bound_ptr(y_bound), _lib.stream_handle(x.device))
     _lib.check(st, "mvs_conv3d_region_fwd")
@@ -1258,15 +1177,10 @@ def _bound_ptr(t):
 def region_split_fragments(weight, device):
     """(split-fp16 MFMA fragments on ``device``, exponent) of a region convolution's weight
     [27][c_out][c_in] (region_weight's layout), formed on the host by mvs_conv3d_region_split_weights."""
-    lib = _lib.load()
-    w = weight.detach().to(device="cpu", dtype=_F32).contiguous()
-    _, cout, cin = w.shape
+    _, cout, cin = weight.shape
     kb = 14 if cin == 16 else 27 * (cin // 32)
-    frag = torch.empty((kb * (cout // 16) * 2 * 64 * 8,), dtype=torch.int16)
-    e = ctypes.c_int(0)
-    st = lib.mvs_conv3d_region_split_weights(_lib.ptr(w), cin, cout, _lib.ptr(frag), ctypes.byref(e))
-    _lib.check(st, "mvs_conv3d_region_split_weights")
-    return frag.to(device), e.value
+    return _host_fragments("mvs_conv3d_region_split_weights", weight, kb * (cout // 16) * 2 * 64 * 8, cin, cout,
+                           device=device)
 
 
 # (the bound words are raised in place; not declared as a mutation: torch's ADInplaceOrView wrapper
@@ -1309,9 +1223,7 @@ def conv3d_region_split(x: torch.Tensor, x2: Optional[torch.Tensor], weight: tor
     frag, ew = derived("region_split", (weight,), lambda wt: region_split_fragments(wt, dev), dev)
     _, cout, cin = weight.shape
     b = x.shape[0]
-    bn = [t if t is None else t.to(device=dev, dtype=_F32).contiguous() for t in (bn_scale, bn_shift, bn_mean)]
-    if any(t is None for t in bn) and not all(t is None for t in bn):
-        raise ValueError("bn_scale, bn_shift and bn_mean go together")
+    bn, bp = _bn_triple(bn_scale, bn_shift, bn_mean, dev)
     ysz = tuple(out_size if store_size is None else store_size)
     shape = (b, cout) + ysz if out_ncdhw else (b,) + ysz + (cout,)
     y = torch.empty(shape, device=dev, dtype=_F32)
@@ -1320,24 +1232,16 @@ def conv3d_region_split(x: torch.Tensor, x2: Optional[torch.Tensor], weight: tor
         slots = split_stats_slots(mode, b, cin, cout, out_size, per_lane, x2 is not None, in_bn is not None)
         if stats.dtype != torch.float64 or stats.numel() != slots * 2 * cout or not stats.is_contiguous():
             raise ValueError("stats: a contiguous float64 tensor of %d x 2 x %d" % (slots, cout))
-    ya = None
-    if y_addend is not None:
-        if tuple(y_addend.shape) != tuple(y.shape) or y_addend.dtype != _F32 or not y_addend.is_contiguous():
-            raise ValueError("y_addend: a contiguous fp32 tensor of the output's shape")
-        ya = _lib.ptr(y_addend)
-    st = lib.mvs_conv3d_region_split_fwd(int(mode), flags, _lib.ptr(x),
-                                         None if x2 is None else _lib.ptr(x2), _lib.ptr(frag), int(ew), _lib.ptr(y),
-                                         b, cin, cout, _ints3(dims), _ints3(out_origin), _ints3(out_size),
-                                         None if in_origin is None else _ints3(in_origin),
-                                         None if in_size is None else _ints3(in_size),
-                                         None if pad is None else _ints3(pad),
-                                         *[None if t is None else _lib.ptr(t) for t in bn], xb,
-                                         _bound_ptr(x2_bound), _bound_ptr(y_bound), ya,
-                                         None if store_origin is None else _ints3(store_origin),
-                                         None if store_size is None else _ints3(store_size),
-                                         None if stats is None else _lib.ptr(stats), None, None,
-                                         None if in_bn is None else _lib.ptr(in_bn.contiguous()),
-                                         _lib.stream_handle(dev))
+    if y_addend is not None and (tuple(y_addend.shape) != tuple(y.shape) or y_addend.dtype != _F32
+                                 or not y_addend.is_contiguous()):
+        raise ValueError("y_addend: a contiguous fp32 tensor of the output's shape")
+    in_bn = in_bn if in_bn is None else in_bn.contiguous()
+    st = lib.mvs_conv3d_region_split_fwd(int(mode), flags, _lib.ptr(x), _opt_ptr(x2), _lib.ptr(frag), int(ew),
+                                         _lib.ptr(y), b, cin, cout, _ints3(dims), _ints3(out_origin),
+                                         _ints3(out_size), _opt_ints3(in_origin), _opt_ints3(in_size),
+                                         _opt_ints3(pad), *bp, xb, _bound_ptr(x2_bound), _bound_ptr(y_bound),
+                                         _opt_ptr(y_addend), _opt_ints3(store_origin), _opt_ints3(store_size),
+                                         _opt_ptr(stats), None, None, _opt_ptr(in_bn), _lib.stream_handle(dev))
     _lib.check(st, "mvs_conv3d_region_split_fwd")
     return y
 
@@ -1479,11 +1383,11 @@ def bn_train_params(bn, s1, s2, count, border=None):
             raise ValueError("border: U [C, C_prev, K], counts [K], prev [3, C_prev]")
         prev = prev.contiguous()
     nbt = bn.num_batches_tracked if track and bn.num_batches_tracked is not None else None
-    pt = lambda t: None if t is None else _lib.ptr(t)
-    st = lib.mvs_bn_train_params(_lib.ptr(sums.contiguous()), c, float(count), pt(bu), pt(bc), cp, ncls, pt(prev),
-                                 _lib.ptr(wt), _lib.ptr(bias), pt(bn.running_mean if track else None),
-                                 pt(bn.running_var if track else None), pt(nbt), float(bn.momentum), float(bn.eps),
-                                 _lib.ptr(params), _lib.stream_handle(dev))
+    st = lib.mvs_bn_train_params(_lib.ptr(sums.contiguous()), c, float(count), _opt_ptr(bu), _opt_ptr(bc), cp, ncls,
+                                 _opt_ptr(prev), _lib.ptr(wt), _lib.ptr(bias),
+                                 _opt_ptr(bn.running_mean if track else None),
+                                 _opt_ptr(bn.running_var if track else None), _opt_ptr(nbt), float(bn.momentum),
+                                 float(bn.eps), _lib.ptr(params), _lib.stream_handle(dev))
     _lib.check(st, "mvs_bn_train_params")
     return params
 
@@ -1506,9 +1410,9 @@ def bn_relu_(x: torch.Tensor, channels_last: bool, scale, shift, mean, r=None, r
         if rr.shape != x.shape:
             raise ValueError("r must have x's shape")
         rs = [f(t) for t in r_bn]
-    pt = lambda t: None if t is None else _lib.ptr(t)
     rc = lib.mvs_bn_relu(_lib.ptr(x), _lib.MVS_LAYOUT_CHANNELS_LAST if channels_last else 0, x.shape[0], c, vox,
-                         pt(sc), pt(sh), pt(mu), pt(rr), *(pt(t) for t in (rs or (None, None, None))), _lib.ptr(x),
+                         _lib.ptr(sc), _lib.ptr(sh), _lib.ptr(mu), _opt_ptr(rr),
+                         *(_opt_ptr(t) for t in (rs or (None, None, None))), _lib.ptr(x),
                          _bound_ptr(y_bound), _lib.stream_handle(x.device))
     _lib.check(rc, "mvs_bn_relu")
     return x

@@ -110,6 +110,49 @@ def test_bf16_channel_quad_is_rounded_fp32(B, V, C, h, w, D):
         assert torch.equal(c16.view(torch.int16), c32.to(torch.bfloat16).view(torch.int16))
 
 
+def test_cost_volume_family_agrees():
+    """The six fused warp + variance ops (one shared wrapper body, six C entry points) on one geometry with
+    two samples of different d_min / d_int (a lost per-sample expansion shows) and d_begin = 1 != d_count (a
+    swapped integer argument shows): every layout / dtype variant holds mvs::cost_volume's values.
+
+    The split volume (C = 8: the split entry takes any C % 4 == 0) re-forms the fp32 values to the bound
+    csrc/split.h documents, piecewise in the scaled value x = |v| 2^e.  x >= 2^-3: 2^-22 relative (hi is a
+    normal fp16, |x - hi| <= 2^-11 x; lo = fp16(x - hi) is off by 2^-11 |x - hi| <= 2^-22 x as a normal
+    fp16, by half the subnormal spacing, 2^-25 <= 2^-22 x, otherwise).  x < 2^-3: |x - hi| < 2^-14, lo is a
+    subnormal and off by at most 2^-25, i.e. 2^(-25 - e) of the value.  (hi + lo is exact in fp32: lo
+    either reaches within 24 bits of hi's leading bit, or is so small that x - hi has no more than 11 bits
+    and lo holds it exactly.)"""
+    from mvs_amd import ops
+    B, V, C, h, w, D = 2, 3, 8, 24, 32, 7
+    K, R, T = camera_batch(B, V, h, w)
+    d_min, d_int = depth_range(B, d_int=6.0, distinct=True)
+    assert d_min[0] != d_min[1] and d_int[0] != d_int[1]
+    f = features(B * V, C, h, w, seed=21).to(DEV)
+    args = (f, K, R, T, d_min, d_int, B, V, 1, D, 25.0)
+    cv, _ = ops.cost_volume(*args)
+    assert cv.shape == (B, C, D, h, w) and cv.dtype == torch.float32 and cv.abs().max() > 0
+    assert not torch.equal(cv[0], cv[1])
+    c4 = ops.cost_volume_c4(*args)
+    assert torch.equal(c4, _to_c4(cv))
+    cv16, _ = ops.cost_volume_bf16(*args)
+    assert cv16.dtype == torch.bfloat16 and torch.equal(cv16.view(torch.int16), cv.to(torch.bfloat16).view(torch.int16))
+    c416 = ops.cost_volume_c4_bf16(*args)
+    assert c416.dtype == torch.bfloat16
+    assert torch.equal(c416.view(torch.int16), c4.to(torch.bfloat16).view(torch.int16))
+    c4a, am = ops.cost_volume_c4_absmax(*args)
+    assert torch.equal(ops.BoundCostVolume(c4a, am).data, c4)
+    scv, ams = ops.cost_volume_c4_split(*args)
+    assert scv.dtype == torch.int32 and scv.shape == c4.shape
+    assert am.dtype == torch.int32 and am.shape == (8,) and torch.equal(am, ams)
+    e = ops.split_exponent(ams)
+    back = ops.unsplit_cost_volume(scv, ams)
+    err, mag = (back - c4).abs(), c4.abs()
+    upper = mag >= 2.0 ** (-3 - e)
+    assert upper.any()
+    assert (err[upper] <= 2.0 ** -22 * mag[upper]).all()
+    assert (err[~upper] <= 2.0 ** (-25 - e)).all()
+
+
 @pytest.mark.parametrize("cout,wino", [(8, True), (8, False), (1, False)])
 def test_narrow_conv_reads_bf16_quads_exactly(cout, wino):
     """conv3d_k3 on the bf16 channel-quad volume == conv3d_k3 on the same values widened to fp32:
