@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "../../include/train/mvs_region_train.h"
 #include "launchers.h"
 
 namespace {
@@ -621,6 +622,39 @@ int mvs_conv3d_k3_wgrad(const float* x, const float* gy, int batch, int c_in, in
   const mvs::LaunchCheck lc;
   mvs::launch_conv3d_wgrad(x, gy, batch, c_in, c_out, d, h, w, static_cast<float*>(workspace), dw,
                            (hipStream_t)stream);
+  return lc.status();
+}
+
+// ---- training extension (include/train/mvs_region_train.h) ----
+int mvs_train_abi_version(void) { return MVS_TRAIN_ABI_VERSION; }
+
+namespace {
+// MVS_OK when mvs_conv3d_region_wgrad can launch on this geometry
+int region_wgrad_geometry(int batch, int channels, const int* in_size) {
+  if (!in_size || batch <= 0 || !mvs::conv3d_region_wgrad_supported(channels)) return MVS_ERR_INVALID_ARGUMENT;
+  uint64_t vox = (uint64_t)batch;
+  for (int k = 0; k < 3; ++k) {
+    if (in_size[k] < 3) return MVS_ERR_INVALID_ARGUMENT;
+    vox *= (uint64_t)in_size[k];
+    if (vox >= (1ull << 31)) return MVS_ERR_TOO_LARGE;   // 32-bit row and tile indices
+  }
+  return MVS_OK;
+}
+}  // namespace
+
+size_t mvs_conv3d_region_wgrad_workspace_bytes(int batch, int channels, const int* in_size) {
+  if (region_wgrad_geometry(batch, channels, in_size) != MVS_OK) return 0;
+  return mvs::conv3d_region_wgrad_workspace_bytes(batch, channels, in_size);
+}
+
+int mvs_conv3d_region_wgrad(const float* x, const float* gy, int batch, int channels, const int* in_size,
+                            float* dw, float* workspace, void* stream) {
+  if (!x || !gy || !dw || !workspace) return MVS_ERR_INVALID_ARGUMENT;
+  if (((uintptr_t)x | (uintptr_t)gy | (uintptr_t)dw | (uintptr_t)workspace) & 15u) return MVS_ERR_INVALID_ARGUMENT;
+  const int st = region_wgrad_geometry(batch, channels, in_size);
+  if (st != MVS_OK) return st;
+  const mvs::LaunchCheck lc;
+  mvs::launch_conv3d_region_wgrad(x, gy, batch, channels, in_size, workspace, dw, (hipStream_t)stream);
   return lc.status();
 }
 

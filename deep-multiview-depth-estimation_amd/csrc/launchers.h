@@ -95,6 +95,12 @@ size_t conv3d_wgrad_workspace_bytes(int B, int c_in, int D, int H, int W);
 bool conv3d_wgrad_supported(int c_in, int c_out);
 void launch_conv3d_wgrad(const float* x, const float* gy, int B, int c_in, int c_out, int D, int H, int W,
                          float* part, float* dw, hipStream_t s);
+// csrc/conv3d_region_wgrad.hip: weight gradient of the stride-1 region convolutions (channels-last padded crop
+// x [B][L...][C], gy [B][L - 2...][C], C in {16, 32, 64}; dw [C][C][27]); part: the workspace
+bool conv3d_region_wgrad_supported(int C);
+size_t conv3d_region_wgrad_workspace_bytes(int B, int C, const int* L);
+void launch_conv3d_region_wgrad(const float* x, const float* gy, int B, int C, const int* L, float* part, float* dw,
+                                hipStream_t s);
 void launch_conv3d_k3_narrow(const float* in, int in_c4, bool wino_z, const float* weight, float* out, int B,
                              int Cin, int Cout, int D, int H, int W, const float* bn_scale, const float* bn_shift,
                              const float* bn_mean, hipStream_t s, const float* in2 = nullptr,

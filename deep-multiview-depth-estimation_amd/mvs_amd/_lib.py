@@ -1,4 +1,5 @@
-"""ctypes binding of the C ABI in ``include/mvs_cost_volume.h`` (libmvs_cost_volume.so).
+"""ctypes binding of the C ABI in ``include/mvs_cost_volume.h`` and of its training extension
+``include/train/mvs_region_train.h`` (libmvs_cost_volume.so).
 
 The library is built in-tree by ``mvs_amd._build.build_library()`` (called from
 ``__graft_entry__.build()``) and travels to the GPU box as a file next to this module.  There is
@@ -105,6 +106,15 @@ SIGNATURES = {
 }
 
 
+# the training extension (include/train/mvs_region_train.h): additive, versioned on its own
+TRAIN_ABI_VERSION = 1
+TRAIN_SIGNATURES = {
+    "mvs_train_abi_version": (_c_int, []),
+    "mvs_conv3d_region_wgrad_workspace_bytes": (ctypes.c_size_t, [_c_int, _c_int, _p]),
+    "mvs_conv3d_region_wgrad": (_c_int, [_p, _p, _c_int, _c_int, _p, _p, _p, _p]),
+}
+
+
 class MVSLibraryError(RuntimeError):
     """The HIP library is missing, stale, or a kernel call failed."""
 
@@ -122,13 +132,17 @@ def load():
             "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950); there is no CPU fallback" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
+    for table in (SIGNATURES, TRAIN_SIGNATURES):
+        for name, (res, args) in table.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
     if lib.mvs_abi_version() != ABI_VERSION:
         raise MVSLibraryError("ABI mismatch: library %d, bindings %d"
                               % (lib.mvs_abi_version(), ABI_VERSION))
+    if lib.mvs_train_abi_version() != TRAIN_ABI_VERSION:
+        raise MVSLibraryError("training-extension ABI mismatch: library %d, bindings %d"
+                              % (lib.mvs_train_abi_version(), TRAIN_ABI_VERSION))
     _lib = lib
     return lib
 

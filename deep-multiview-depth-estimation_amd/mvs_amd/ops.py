@@ -733,6 +733,36 @@ def conv3d_k3_wgrad(x: torch.Tensor, gy: torch.Tensor) -> torch.Tensor:
     return dw
 
 
+REGION_WGRAD_CHANNELS = (16, 32, 64)   # c_in = c_out of mvs_conv3d_region_wgrad
+
+
+def conv3d_region_wgrad(x_cl: torch.Tensor, gy_cl: torch.Tensor) -> torch.Tensor:
+    """Weight gradient of a stride-1 region convolution nn.Conv3d(C, C, 3, padding=0, bias=False)
+    (model.py:108-113 conv_k_1 on the padded crop) from its channels-last input x_cl [B, Lz, Ly, Lx, C] and
+    output gradient gy_cl [B, Lz-2, Ly-2, Lx-2, C]: dw [C, C, 3, 3, 3] on the f32 matrix cores
+    (mvs_conv3d_region_wgrad of the training extension, deterministic).  C in REGION_WGRAD_CHANNELS."""
+    _require_gpu(x_cl, "x_cl")
+    lib = _lib.load()
+    if (x_cl.dim() != 5 or gy_cl.dim() != 5 or x_cl.shape[0] != gy_cl.shape[0] or x_cl.shape[4] != gy_cl.shape[4]
+            or tuple(d - 2 for d in x_cl.shape[1:4]) != tuple(gy_cl.shape[1:4])):
+        raise ValueError("x_cl [B, Lz, Ly, Lx, C] and gy_cl [B, Lz-2, Ly-2, Lx-2, C] expected")
+    b, c = x_cl.shape[0], x_cl.shape[4]
+    if c not in REGION_WGRAD_CHANNELS:
+        raise ValueError("C = %d not in %s" % (c, REGION_WGRAD_CHANNELS))
+    x_cl = x_cl.to(_F32).contiguous()
+    gy_cl = gy_cl.to(device=x_cl.device, dtype=_F32).contiguous()
+    size = _ints3(x_cl.shape[1:4])
+    nbytes = lib.mvs_conv3d_region_wgrad_workspace_bytes(b, c, size)
+    if nbytes == 0:
+        raise ValueError("crop %s: every extent >= 3 and B * Lz * Ly * Lx < 2^31 expected" % (tuple(x_cl.shape[1:4]),))
+    ws = torch.empty(nbytes // 4, device=x_cl.device, dtype=_F32)
+    dw = torch.empty((c, c, 3, 3, 3), device=x_cl.device, dtype=_F32)
+    st = lib.mvs_conv3d_region_wgrad(_lib.ptr(x_cl), _lib.ptr(gy_cl), b, c, size, _lib.ptr(dw), _lib.ptr(ws),
+                                     _lib.stream_handle(x_cl.device))
+    _lib.check(st, "mvs_conv3d_region_wgrad")
+    return dw
+
+
 @torch.library.custom_op("mvs::conv_head_fp32", mutates_args=())
 def conv_head_fp32(cv4: torch.Tensor, w0: torch.Tensor, bn0_scale: Optional[torch.Tensor],
                    bn0_shift: Optional[torch.Tensor], bn0_mean: Optional[torch.Tensor], w1: torch.Tensor,

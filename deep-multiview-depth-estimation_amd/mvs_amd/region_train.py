@@ -8,7 +8,9 @@ conv3d_box / conv_transpose3d_box).  The tap GEMMs accumulate every tap's produc
   stride-2 conv_k_0 (model.py:101-107, stacked 32 -> 16 + 32 + 64 over R2)  mode S2, one launch per layer
   stride-1 conv_k_1 (model.py:108-113, on R1 from the padded R2 crop)         mode S1
   transposed deconv_3_0 / deconv_2_0 (model.py:117-120, the full box from M)  mode T2
-MVS_TRAIN_REGION_FWD selects which (enabled())."""
+MVS_TRAIN_REGION_FWD selects which (enabled()).  MVS_TRAIN_REGION_BWD (bwd_enabled(), default "taps") moves
+the stride-1 layers' backward onto HIP kernels as well: the input gradient on the forward's region kernel
+in its adjoint geometry, the weight gradient on csrc/conv3d_region_wgrad.hip."""
 import os
 
 import torch
@@ -28,6 +30,18 @@ def enabled(x, kind=None):
     v = os.environ.get("MVS_TRAIN_REGION_FWD", "s1,t2")
     on = v == "hip" or (kind is not None and kind in v.split(","))
     return on and x.is_cuda and x.dtype == torch.float32 and torch.is_grad_enabled()
+
+
+BWD_KINDS = ("s1",)               # kinds with a HIP backward
+S1_BWD_CHANNELS = (16, 32, 64)    # channel counts of "s1" whose HIP backward beats the tap GEMMs
+
+
+def bwd_enabled(kind, channels=None):
+    """The backward of ``kind`` runs on the HIP kernels.  MVS_TRAIN_REGION_BWD, read on every call: a comma
+    list of kinds, "hip" (every kind in BWD_KINDS) or "taps" (none: the per-tap GEMMs; the default)."""
+    v = os.environ.get("MVS_TRAIN_REGION_BWD", "taps")
+    on = kind in BWD_KINDS and (v == "hip" or kind in v.split(","))
+    return on and (kind != "s1" or channels is None or channels in S1_BWD_CHANNELS)
 
 
 def _region_w(w):      # Conv3d weight [co, ci, 3, 3, 3] -> [27][co][ci]
@@ -65,24 +79,45 @@ class _S2Box(torch.autograd.Function):
         return gx, gw, None, None, None, None
 
 
+def _region_w_adjoint(w):   # Conv3d weight [co, ci, 3, 3, 3] -> the input gradient's [27][ci][co], taps flipped
+    return w.detach().flip(2, 3, 4).permute(2, 3, 4, 1, 0).reshape(27, w.shape[1], w.shape[0]).contiguous()
+
+
 class _S1Valid(torch.autograd.Function):
-    """conv3d(xin, w) with padding 0 (xin: the zero-padded crop of _conv_s1_region)."""
+    """conv3d(xin, w) with padding 0 (xin: the zero-padded crop of _conv_s1_region).  With the HIP backward
+    (bwd_enabled("s1", C)) the channels-last copy the forward makes anyway is what is saved, and the backward is
+      d/dw  gw[co][ci][t] = sum gy[o][co] x[o + t][ci]                 ops.conv3d_region_wgrad
+      d/dx  gx[i] = sum_t gy[i - t] w[.][.][t] = conv(gy, w~) on the box of xin, gy zero outside its own:
+            the forward's region kernel with gy as the input region at origin 1 of a volume of xin's
+            extent, w~[t][ci][co] = w[co][ci][2 - t] per dim."""
 
     @staticmethod
     def forward(ctx, xin, w):
         from .ops import CONV_S1, conv3d_region
         L = list(xin.shape[2:])
         out = [d - 2 for d in L]
-        y = conv3d_region(xin.permute(0, 2, 3, 4, 1).contiguous(), None, _region_w(w), CONV_S1, L, [1, 1, 1], out,
-                          [0, 0, 0], L, None)
-        ctx.save_for_backward(xin, w)
+        x_cl = xin.permute(0, 2, 3, 4, 1).contiguous()
+        y = conv3d_region(x_cl, None, _region_w(w), CONV_S1, L, [1, 1, 1], out, [0, 0, 0], L, None)
+        ctx.hip_bwd = bwd_enabled("s1", w.shape[0])
+        ctx.save_for_backward(x_cl if ctx.hip_bwd else xin, w)
         ctx.out = tuple(out)
         return _cf(y)
 
     @staticmethod
     def backward(ctx, gy):
         xin, w = ctx.saved_tensors
-        gx, gw = tap_gemm.conv3d_backward(xin, w, 1, 0, ctx.out, gy, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        if not ctx.hip_bwd:
+            return tap_gemm.conv3d_backward(xin, w, 1, 0, ctx.out, gy, ctx.needs_input_grad[0],
+                                            ctx.needs_input_grad[1])
+        from .ops import CONV_S1, conv3d_region, conv3d_region_wgrad
+        gy_cl = gy.permute(0, 2, 3, 4, 1).contiguous()
+        gx = gw = None
+        if ctx.needs_input_grad[0]:
+            L = list(xin.shape[1:4])
+            gx = _cf(conv3d_region(gy_cl, None, _region_w_adjoint(w), CONV_S1, L, [0, 0, 0], L, [1, 1, 1],
+                                   list(ctx.out), None, per_lane=True))
+        if ctx.needs_input_grad[1]:
+            gw = conv3d_region_wgrad(xin, gy_cl)
         return gx, gw
 
 

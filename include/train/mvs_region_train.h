@@ -1,0 +1,45 @@
+/* mvs_region_train.h -- training extension of libmvs_cost_volume.so: entry points that only the
+ * autograd backward of the regulariser's region convolutions uses (mvs_amd/region_train.py).
+ *
+ * This surface is additive and versioned on its own (MVS_TRAIN_ABI_VERSION): the drop-in contract of
+ * include/mvs_cost_volume.h (MVS_ABI_VERSION) does not change when it grows.  Status codes, pointer and
+ * stream conventions are those of mvs_cost_volume.h: every pointer is a DEVICE pointer unless stated,
+ * `stream` is a hipStream_t (NULL: the default stream), nothing allocates or synchronises.
+ */
+#ifndef MVS_REGION_TRAIN_H
+#define MVS_REGION_TRAIN_H
+
+#include <stddef.h>
+
+#include "../mvs_cost_volume.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define MVS_TRAIN_ABI_VERSION 1
+
+/* Training-extension ABI version of the loaded library (MVS_TRAIN_ABI_VERSION at build time). */
+int mvs_train_abi_version(void);
+
+/* Weight gradient of a stride-1 region convolution nn.Conv3d(C, C, 3, padding=0, bias=False) applied to
+ * the zero-padded crop (model.py:108-113 conv_1_1 / conv_2_1 / conv_3_1 through _conv_s1_region):
+ *   dw[co][ci][tz][ty][tx] = sum over b and every output voxel o of gy[b][o][co] * x[b][o + t][ci]
+ * fp32 products and sums on the f32-input matrix cores, partial sums per workgroup reduced in a fixed
+ * order (bit-reproducible; no atomics; the workspace need not be zeroed).
+ *   x  [batch][Lz][Ly][Lx][channels]            channels-last padded crop, in_size = {Lz, Ly, Lx} (HOST)
+ *   gy [batch][Lz-2][Ly-2][Lx-2][channels]      channels-last output gradient
+ *   dw [channels][channels][3][3][3]            nn.Conv3d's weight layout
+ * x, gy, dw and workspace contiguous fp32 with 16-byte-aligned bases; channels in {16, 32, 64}; every
+ * in_size[k] >= 3; batch * Lz * Ly * Lx < 2^31 (else MVS_ERR_TOO_LARGE).
+ * workspace: mvs_conv3d_region_wgrad_workspace_bytes(batch, channels, in_size) bytes (0 for arguments
+ * the launch would refuse). */
+size_t mvs_conv3d_region_wgrad_workspace_bytes(int batch, int channels, const int* in_size);
+int mvs_conv3d_region_wgrad(const float* x, const float* gy, int batch, int channels, const int* in_size,
+                            float* dw, float* workspace, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* MVS_REGION_TRAIN_H */
