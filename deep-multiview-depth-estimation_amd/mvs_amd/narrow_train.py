@@ -8,7 +8,8 @@ padding 1)) on the HIP kernels, fp32:
   d/dw           gw[co][ci][t] = sum gy x(t)    mvs_conv3d_k3_wgrad (csrc/conv3d_wgrad.hip, f32 MFMA)
 
 They replace the per-tap rocBLAS GEMMs (tap_gemm.py), which stream the full volume once per tap in each
-pass (cfg 2: 112 ms for conv_0_0's forward + backward, 106 ms for conv_out's; tools/train_layers.py)."""
+pass (cfg 2: 112 ms for conv_0_0's forward + backward, 106 ms for conv_out's; the per-layer
+tool that measured it is no longer in the tree)."""
 import os
 
 import torch

@@ -1114,8 +1114,8 @@ def derived(tag, tensors, fn, device=None):
 
 
 def _pipeline_lane():
-    from . import model
-    return model._LANE[0]
+    from . import streams
+    return streams._LANE[0]
 
 
 def clear_derived():
@@ -1381,10 +1381,10 @@ def channel_stats(x: torch.Tensor, channels_last: bool):
 def bn_train_params(bn, s1, s2, count, border=None):
     """Train-mode BatchNorm parameters [3, C] = (scale, shift, mean) from the float64 batch sums s1, s2
     over ``count`` elements, updating bn's running statistics and num_batches_tracked (mvs_bn_train_params,
-    csrc/channel_ops.hip: one launch for what model._bn_train does in ~12 device ops).  ``border``: None
+    csrc/channel_ops.hip: one launch for what bn_sums._bn_train does in ~12 device ops).  ``border``: None
     or (U [C, C_prev, K] float64, counts [K] float64, prev [3, C_prev]) -- conv_k_1's border-class term
-    (model._border_class_sums) with the previous BN's constant relu(BN(0)) formed from its parameters
-    ``prev``.  bn.momentum must be set (None: the cumulative average, model._bn_train)."""
+    (bn_sums._border_class_sums) with the previous BN's constant relu(BN(0)) formed from its parameters
+    ``prev``.  bn.momentum must be set (None: the cumulative average, bn_sums._bn_train)."""
     lib = _lib.load()
     if bn.momentum is None:
         raise ValueError("bn_train_params: momentum=None (cumulative average) is model._bn_train's")

@@ -16,6 +16,7 @@ import os
 import torch
 
 from . import tap_gemm
+from .regions import extent, origin
 
 S2_SPLITS = (16, 32, 64)   # conv_1_0, conv_2_0, conv_3_0 output channels (the stacked S2 order)
 S1_CHANNELS = (16, 32, 64)
@@ -61,7 +62,7 @@ class _S2Box(torch.autograd.Function):
     def forward(ctx, x, w, out_reg, pad, pad_lo, splits):
         from .ops import CONV_S2, conv3d_region
         n = list(x.shape[2:])
-        org, size = [lo for lo, _ in out_reg], [hi - lo + 1 for lo, hi in out_reg]
+        org, size = origin(out_reg), extent(out_reg)
         xc = x.contiguous()
         ys, c0 = [], 0
         for co in splits:
@@ -125,10 +126,9 @@ class _T2Box(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, x_reg, out_reg, pad, dims, crop):
         from .ops import CONV_T2, conv3d_region
-        org, size = [lo for lo, _ in out_reg], [hi - lo + 1 for lo, hi in out_reg]
-        xorg, xsize = [lo for lo, _ in x_reg], [hi - lo + 1 for lo, hi in x_reg]
-        y = conv3d_region(x.permute(0, 2, 3, 4, 1).contiguous(), None, _region_wt(w), CONV_T2, list(dims), org, size,
-                          xorg, xsize, list(pad))
+        size = extent(out_reg)
+        y = conv3d_region(x.permute(0, 2, 3, 4, 1).contiguous(), None, _region_wt(w), CONV_T2, list(dims),
+                          origin(out_reg), size, origin(x_reg), extent(x_reg), list(pad))
         ctx.save_for_backward(x, w)
         ctx.geo = (tuple(crop), tuple(size))
         return _cf(y)

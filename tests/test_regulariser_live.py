@@ -84,9 +84,20 @@ def test_train_mode_live_autograd_equals_full_volume(shape, taps, monkeypatch):
     rounding (CostVolumeReg.live_autograd_ok routes HIP fp32 training through it).  ``taps``: the
     region convolutions through the HIP path's per-tap GEMM boxes (tap_gemm.conv3d_box /
     conv_transpose3d_box), here in float64 on the CPU."""
+    calls = {"conv3d_box": 0, "conv_transpose3d_box": 0}
     if taps:
-        from mvs_amd import model as model_mod
-        monkeypatch.setattr(model_mod, "_taps", lambda x: torch.is_grad_enabled())
+        from mvs_amd import regions, tap_gemm
+        monkeypatch.setattr(regions, "_taps", lambda x: torch.is_grad_enabled())
+
+        def counting(name):
+            fn = getattr(tap_gemm, name)
+
+            def wrapper(*args, **kwargs):
+                calls[name] += 1
+                return fn(*args, **kwargs)
+            return wrapper
+        for name in calls:
+            monkeypatch.setattr(tap_gemm, name, counting(name))
     D, h, w = shape
     ms = [_reg(D, h, w, seed=5).double().train() for _ in range(2)]
     cv = torch.rand(2, 32, D, h, w, generator=torch.Generator().manual_seed(D + 31 * w), dtype=torch.float64)
@@ -98,6 +109,8 @@ def test_train_mode_live_autograd_equals_full_volume(shape, taps, monkeypatch):
         (y * g).sum().backward()
         outs.append(y.detach())
         xgrads.append(x.grad)
+    if taps:   # (the patch reached the region helpers: the per-tap GEMM boxes ran)
+        assert calls["conv3d_box"] >= 1 and calls["conv_transpose3d_box"] >= 1, calls
     torch.testing.assert_close(outs[1], outs[0], rtol=1e-10, atol=1e-13)
     torch.testing.assert_close(xgrads[1], xgrads[0], rtol=1e-9, atol=1e-13)
     p_full, p_live = dict(ms[0].named_parameters()), dict(ms[1].named_parameters())

@@ -8,14 +8,14 @@ from cameras import camera_batch, depth_range
 from mvs_amd import ops
 from mvs_amd.config import pad_outpad
 from mvs_amd import model as M
+from mvs_amd.regions import live_regions
 DEV = torch.device("cuda", 0)
 RUNS = [0]
 CFGS = [(1, 3, 48, 28, 64), (1, 3, 24, 28, 64), (1, 3, 32, 32, 48), (1, 3, 48, 32, 48)]
 if os.environ.get('HEAD_DIFF_BIG'): CFGS = [(4, 3, 192, 128, 160)] * int(os.environ['HEAD_DIFF_BIG'])
 for (B, V, D, h, w) in CFGS:
     pad = list(pad_outpad(D, h, w)[0]); n = (D, h, w)
-    full = tuple((0, d - 1) for d in n)
-    Bq = M._tconv_input_region(full, n, pad); C2 = M._tconv_input_region(Bq, n, pad)
+    _, Bq, C2, _ = live_regions(n, pad)
     h1, h2 = M._grow(Bq, n, 1), M._grow(C2, n, 1)
     lo = [max(2 * a - p, 0) for (a, _), p in zip(h2, pad)]
     hi = [min(2 * b - p + 2, d - 1) + 1 for (_, b), p, d in zip(h2, pad, n)]

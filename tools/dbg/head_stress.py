@@ -21,6 +21,7 @@ from cameras import camera_batch, depth_range  # noqa: E402
 from mvs_amd import model as M  # noqa: E402
 from mvs_amd import ops  # noqa: E402
 from mvs_amd.config import pad_outpad  # noqa: E402
+from mvs_amd.regions import live_regions  # noqa: E402
 
 DEV = torch.device("cuda", 0)
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 50
@@ -45,9 +46,7 @@ def where(bad, tag):
 for (B, V, D, h, w) in CFGS:
     pad = list(pad_outpad(D, h, w)[0])
     n = (D, h, w)
-    full = tuple((0, d - 1) for d in n)
-    Bq = M._tconv_input_region(full, n, pad)
-    C2 = M._tconv_input_region(Bq, n, pad)
+    _, Bq, C2, _ = live_regions(n, pad)
     h1, h2 = M._grow(Bq, n, 1), M._grow(C2, n, 1)
     lo = [max(2 * a - p, 0) for (a, _), p in zip(h2, pad)]
     hi = [min(2 * b - p + 2, d - 1) + 1 for (_, b), p, d in zip(h2, pad, n)]

@@ -13,7 +13,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 import bench  # noqa: E402
 import torch  # noqa: E402
-from mvs_amd import model as M  # noqa: E402
+from mvs_amd import model as M, regions, streams  # noqa: E402
 from mvs_amd.ops import (CONV_S1, CONV_S2, CONV_T2, conv3d_k3, conv3d_region, conv_head_fp32,  # noqa: E402
                          deconv3d_k3s2, region_weight, softmax_depth)
 
@@ -46,12 +46,8 @@ def main():
         feats = net.feature_encoder(img)
         cv = warp_and_assemble_cost_volume(K, R, T, d_min, d_int, feats, B, V, d_num=D, channel_quads=True)[0].data
         n = tuple(cv.shape[2:5])
-        full = tuple((0, d - 1) for d in n)
-        Bq = M._tconv_input_region(full, n, reg.pad)
-        C2 = M._tconv_input_region(Bq, n, reg.pad)
-        C3 = M._tconv_input_region(C2, n, reg.pad)
-        org = lambda r: [lo for lo, _ in r]
-        size = lambda r: [hi - lo + 1 for lo, hi in r]
+        _, Bq, C2, C3 = regions.live_regions(n, reg.pad)
+        org, size = regions.origin, regions.extent
         dims, pad = list(n), list(reg.pad)
         bn = M._bn_eval
         layers = {"conv_0_0": lambda: conv3d_k3(cv, reg.conv_0_0.weight, *bn(reg.BN_0), in_c4=True, wino_z=True)}
@@ -105,12 +101,12 @@ def main():
             timed(name, layers[name], a.reps)
         if a.only:
             return
-        saved = M._side_stream
-        M._side_stream = lambda device, which=0, priority=0: torch.cuda.current_stream(device)
+        saved = streams._side_stream
+        streams._side_stream = lambda device, which=0, priority=0: torch.cuda.current_stream(device)
         try:
             timed("eval step (serialised)", step, a.reps)
         finally:
-            M._side_stream = saved
+            streams._side_stream = saved
 
 
 if __name__ == "__main__":

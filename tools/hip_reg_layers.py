@@ -14,7 +14,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 import bench  # noqa: E402
 import torch  # noqa: E402
-from mvs_amd import model as M  # noqa: E402
+from mvs_amd import model as M, regions, streams  # noqa: E402
 from mvs_amd.ops import conv_s2_split, split_head  # noqa: E402
 from mvs_amd.ops import (CONV_S1, CONV_S2, CONV_T2, conv3d_k3, conv3d_k3_split, conv3d_region,  # noqa: E402
                          deconv3d_k3s2, region_weight, softmax_depth)
@@ -51,12 +51,8 @@ def main():
                                                   split=True)
         cv, cvs, bound = cv.data, cvs.data, cvs.absmax   # BoundCostVolume: (volume, bound words)
         n = tuple(cv.shape[2:5])
-        full = tuple((0, d - 1) for d in n)
-        Bq = M._tconv_input_region(full, n, reg.pad)
-        C2 = M._tconv_input_region(Bq, n, reg.pad)
-        C3 = M._tconv_input_region(C2, n, reg.pad)
-        org = lambda r: [lo for lo, _ in r]
-        size = lambda r: [hi - lo + 1 for lo, hi in r]
+        _, Bq, C2, C3 = regions.live_regions(n, reg.pad)
+        org, size = regions.origin, regions.extent
         dims, pad = list(n), list(reg.pad)
         bn = M._bn_eval
         layers = {}
@@ -138,12 +134,12 @@ def main():
         reg.split_f16 = False
         timed("eval step (exact fp32 conv_0_0)", step, a.reps)
         reg.split_f16 = True
-        saved = M._side_stream
-        M._side_stream = lambda device, which=0, priority=0: torch.cuda.current_stream(device)
+        saved = streams._side_stream
+        streams._side_stream = lambda device, which=0, priority=0: torch.cuda.current_stream(device)
         try:
             timed("eval step (serialised)", step, a.reps)
         finally:
-            M._side_stream = saved
+            streams._side_stream = saved
 
 
 if __name__ == "__main__":

@@ -13,6 +13,7 @@ import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402,F401
 from mvs_amd import model as M  # noqa: E402
 from mvs_amd.config import pad_outpad  # noqa: E402
+from mvs_amd.regions import live_regions  # noqa: E402
 
 
 def timed(name, fn, n=3):
@@ -35,10 +36,7 @@ def main():
     reg = M.CostVolumeReg(pad=pad, outpad=outpad).to(dev).eval()
     cv = torch.randn(B, 32, D, h, w, device=dev)
     n = (D, h, w)
-    full = tuple((0, d - 1) for d in n)
-    Bq = M._tconv_input_region(full, n, pad)
-    C2 = M._tconv_input_region(Bq, n, pad)
-    C3 = M._tconv_input_region(C2, n, pad)
+    full, Bq, C2, C3 = live_regions(n, pad)
     print("regions", Bq, C2, C3, flush=True)
     with torch.no_grad():
         y0 = timed("conv_0_0 full (MIOpen)", lambda: reg.conv_0_0(cv))
