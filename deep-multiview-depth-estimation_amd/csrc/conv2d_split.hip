@@ -25,27 +25,20 @@
 // (L2) are fetched one K block ahead.  The epilogue unscales, applies BN + ReLU, stores NCHW (4 consecutive pixels per lane) and
 // raises the output's bound words for the next layer.
 #include "launchers.h"
-#include "packed.h"
-#include "split.h"
+#include "region_conv.h"   // the split-record LDS tile (SplitRec) and kOob
 
 namespace mvs {
 namespace {
 
-typedef _Float16 h8v __attribute__((ext_vector_type(8)));
-constexpr uint32_t kOob2 = 0xFFFFFFC0u;   // out-of-range buffer offset: loads return 0
-
 template <int CI, int K, int S, int RB, int XB>
-struct Tile2 {
+struct Tile2 : SplitRec<CI> {
   static constexpr int TX = 16 * XB, TY = 4 * (RB / XB);
   static constexpr int IW = (TX - 1) * S + K, IH = (TY - 1) * S + K, PV = IW * IH;
   static constexpr int HALF = (IW + 1) / 2;   // S = 2: even columns at 0 .., odd ones from HALF
-  static constexpr int REC = CI * 4;          // bytes per pixel record
-  static constexpr int NCH = REC / 16;        // 16-byte chunks per record: 2 / 4 / 8
-  static constexpr int LDS = PV * REC;
+  static constexpr int LDS = PV * SplitRec<CI>::REC;
   static constexpr int TPB = 32 / CI;         // taps per K-32 block
   static constexpr int KB = (K * K + TPB - 1) / TPB;
   __device__ static int col(int px) { return S == 1 ? px : (px & 1) * HALF + (px >> 1); }
-  __device__ static int chunk_off(int v, int c) { return v * REC + ((c ^ ((v / (16 / NCH)) % NCH)) << 4); }
 };
 
 __device__ inline float row_ror8(float x) {   // lane l <- lane (l + 8) mod 16 of its row
@@ -89,7 +82,7 @@ __global__ __launch_bounds__(kBlock) void conv2d_split_kernel(
         const int px = e % T::IW, py = (e / T::IW) % T::IH, q = e / T::PV;
         const int gx = ix0 + px, gy = iy0 + py;
         const bool ok = k0 + k < PER && e < NIT && gx >= 0 && gx < W && gy >= 0 && gy < H;
-        const uint32_t off = ok ? (uint32_t)(((size_t)(4 * q) * H + gy) * W + gx) * 4u : kOob2;
+        const uint32_t off = ok ? (uint32_t)(((size_t)(4 * q) * H + gy) * W + gx) * 4u : kOob;
         const uint32_t ps = ok ? (uint32_t)(plane * 4) : 0u;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
@@ -215,8 +208,7 @@ void launch_split2d_tile(const float* x, const void* wf, int w_exp, float* y, in
   const int Ho = (H + 2 * (K / 2) - K) / S + 1, Wo = (W + 2 * (K / 2) - K) / S + 1;
   const int tiles_x = (Wo + T::TX - 1) / T::TX, tiles_y = (Ho + T::TY - 1) / T::TY;
   const int tiles = tiles_x * tiles_y;
-  const dim3 grid((unsigned)((tiles + 7) / 8 * 8), (unsigned)N);
-  hipLaunchKernelGGL((conv2d_split_kernel<CI, CO, K, S, RB, XB>), grid, dim3(kBlock), 0, s, x,
+  hipLaunchKernelGGL((conv2d_split_kernel<CI, CO, K, S, RB, XB>), tile_grid(tiles, N), dim3(kBlock), 0, s, x,
                      reinterpret_cast<const h8v*>(wf), w_exp, y, H, W, Ho, Wo, tiles_x, tiles, sc, sh, mu, xb, yb);
 }
 

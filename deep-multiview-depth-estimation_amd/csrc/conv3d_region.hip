@@ -1,5 +1,5 @@
-// conv3d_region.hip -- the regulariser's region convolutions (CostVolumeReg, model.py:76-95, forward
-// at model.py:101-121) as implicit GEMMs on the fp32 matrix cores (v_mfma_f32_16x16x4_f32: exact
+// conv3d_region.hip -- the regulariser's region convolutions (CostVolumeReg, regulariser.py; the
+// reference's model.py:76-121) as implicit GEMMs on the fp32 matrix cores (v_mfma_f32_16x16x4_f32: exact
 // fp32, one rounding per product, the f32 VALU's peak rate without its operand traffic), with the
 // eval-mode BatchNorm + ReLU that follows every one of them fused into the epilogue.
 //
@@ -26,23 +26,12 @@
 #include <cstdlib>
 
 #include "launchers.h"
-#include "packed.h"
-#include "split.h"
+#include "region_conv.h"
 
 namespace mvs {
 namespace {
 
-typedef f4v f4v_t;
-// out-of-range buffer offset for taps without input (the loads return 0); every descriptor built
-// here covers less than 2^32 - 64 bytes (mvs_conv3d_region_fwd checks)
-constexpr uint32_t kOob = 0xFFFFFFC0u;
-
-// output voxels per wave: RB MFMA row blocks of 16 (template; 2 by default)
-
-template <int MODE>
-struct ConvMode {};
-constexpr int kS1 = 0, kS2 = 1, kT2 = 2;
-
+// (output voxels per wave: RB MFMA row blocks of 16 -- template; 2 by default)
 struct Geo {
   int n[3];     // volume dims (D, H, W)
   int o0[3];    // output region origin
@@ -58,12 +47,6 @@ struct Geo {
   int st0[3];   // the output region's place in the stored tensor: y holds a box of size stn whose
   int stn[3];   //   voxel st0 is the region's first (default 0 / on: y is the region)
 };
-
-// T2 parity class: per dim, outputs o with (o + P) % 2 == par; first such o in the region and count
-__device__ inline void class_dim(int o0, int on, int p, int par, int& first, int& cnt) {
-  first = o0 + (((o0 + p) & 1) != par ? 1 : 0);
-  cnt = first < o0 + on ? (o0 + on - 1 - first) / 2 + 1 : 0;
-}
 
 __device__ inline void store_out(float* __restrict__ y, const Geo& g, int b, int co, int vz, int vy, int vx,
                                  int CO, float v) {
@@ -152,17 +135,17 @@ __device__ __forceinline__ void region_conv(
     lin[rb] = (bs[0] * lim[1] + bs[1]) * lim[2] + bs[2];
   }
 
-  f4v_t acc[RB][NB];
+  f4v acc[RB][NB];
 #pragma unroll
   for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
-    for (int nb = 0; nb < NB; ++nb) acc[rb][nb] = f4v_t{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int nb = 0; nb < NB; ++nb) acc[rb][nb] = f4v{0.0f, 0.0f, 0.0f, 0.0f};
 
   // buffer descriptors (workgroup-uniform bases; out-of-range offsets read 0): S2 the sample's
   // volume (channel-quad: quads cb*4 .. cb*4+3 per channel block; NCDHW: 16 channel planes per
   // block), S1 / T2 the sample's region tensor (and addend)
   const size_t rvol = (size_t)g.in[0] * g.in[1] * g.in[2];
-  const size_t nvol = rvol;   // S2: voxels of the (boxed) volume per channel plane / quad plane
+  // (S2: rvol = voxels of the (boxed) volume per channel plane / quad plane)
   const int sy = lim[2], sz = lim[1] * lim[2];
   // ---- K loop: taps by rows (tz, ty); per row and 16-channel block the A values of its (up to)
   // three x taps and every row block and the matching weights are loaded together, then fed to
@@ -193,42 +176,42 @@ __device__ __forceinline__ void region_conv(
         Rsrc rs, rs2;
         if constexpr (MODE == kS2) {
           if constexpr (QM == 2)   // bf16 quads: 8 bytes per voxel and quad
-            rs = make_rsrc(reinterpret_cast<const char*>(x) + ((size_t)b * (CI / 4) + cb * 4) * nvol * 8,
-                           (uint32_t)(nvol * 32));
+            rs = make_rsrc(reinterpret_cast<const char*>(x) + ((size_t)b * (CI / 4) + cb * 4) * rvol * 8,
+                           (uint32_t)(rvol * 32));
           else if constexpr (QM == 1 || QM == 3)
-            rs = make_rsrc(x + ((size_t)b * (CI / 4) + cb * 4) * nvol * 4, (uint32_t)(nvol * 64));
+            rs = make_rsrc(x + ((size_t)b * (CI / 4) + cb * 4) * rvol * 4, (uint32_t)(rvol * 64));
           else
-            rs = make_rsrc(x + ((size_t)b * CI + cb * 16) * nvol, (uint32_t)(nvol * 64));
+            rs = make_rsrc(x + ((size_t)b * CI + cb * 16) * rvol, (uint32_t)(rvol * 64));
         } else {
           rs = make_rsrc(x + (size_t)b * rvol * CI, (uint32_t)(rvol * CI * 4));
           if (x2) rs2 = make_rsrc(x2 + (size_t)b * rvol * CI, (uint32_t)(rvol * CI * 4));
         }
-        f4v_t a[3][RB], bw[3][NB];
+        f4v a[3][RB], bw[3][NB];
 #pragma unroll
         for (int tx = 0; tx < 3; ++tx) {
           if (MODE == kT2 && ((tx & 1) != par[2])) continue;
 #pragma unroll
           for (int rb = 0; rb < RB; ++rb) {
             const uint32_t vx = vox[tx][rb];
-            f4v_t v;
+            f4v v;
             if constexpr (MODE == kS2) {
               if constexpr (QM == 2) {   // the bf16 quad: one 8-byte load, widened (exact)
                 typedef __attribute__((ext_vector_type(2))) unsigned v2u;
                 const v2u p = __builtin_amdgcn_raw_buffer_load_b64(
-                    rs, (int)(vx == kOob ? kOob : ((uint32_t)kq * (uint32_t)nvol + vx) * 8u), 0, 0);
-                v = f4v_t{__uint_as_float(p.x << 16), __uint_as_float(p.x & 0xFFFF0000u),
+                    rs, (int)(vx == kOob ? kOob : ((uint32_t)kq * (uint32_t)rvol + vx) * 8u), 0, 0);
+                v = f4v{__uint_as_float(p.x << 16), __uint_as_float(p.x & 0xFFFF0000u),
                           __uint_as_float(p.y << 16), __uint_as_float(p.y & 0xFFFF0000u)};
               } else if constexpr (QM == 3) {   // split quad: 16-byte load, (hi + lo) 2^-sx (exact sum)
                 v = unsplit4(__builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(
-                                 rs, (int)(vx == kOob ? kOob : ((uint32_t)kq * (uint32_t)nvol + vx) * 16u), 0, 0)),
+                                 rs, (int)(vx == kOob ? kOob : ((uint32_t)kq * (uint32_t)rvol + vx) * 16u), 0, 0)),
                              sx);
               } else if constexpr (QM == 1) {   // the quad (c4 / 4) of the voxel: one 16-byte load
-                v = ld4(rs, vx == kOob ? kOob : ((uint32_t)kq * (uint32_t)nvol + vx) * 16u, 0);
+                v = ld4(rs, vx == kOob ? kOob : ((uint32_t)kq * (uint32_t)rvol + vx) * 16u, 0);
               } else {
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
                   v[q] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
-                      rs, (int)(vx == kOob ? kOob : ((uint32_t)(kq * 4 + q) * (uint32_t)nvol + vx) * 4u), 0, 0));
+                      rs, (int)(vx == kOob ? kOob : ((uint32_t)(kq * 4 + q) * (uint32_t)rvol + vx) * 4u), 0, 0));
               }
             } else {
               const uint32_t eo = vx == kOob ? kOob : (vx * (uint32_t)CI + (uint32_t)c4) * 4u;
@@ -240,7 +223,7 @@ __device__ __forceinline__ void region_conv(
           const float* wt = w + (size_t)((tz * 3 + ty) * 3 + tx) * CO * CI;
 #pragma unroll
           for (int nb = 0; nb < NB; ++nb)
-            bw[tx][nb] = *reinterpret_cast<const f4v_t*>(wt + (size_t)(nb * 16 + m) * CI + c4);
+            bw[tx][nb] = *reinterpret_cast<const f4v*>(wt + (size_t)(nb * 16 + m) * CI + c4);
         }
 #pragma unroll
         for (int tx = 0; tx < 3; ++tx) {
@@ -305,19 +288,11 @@ __global__ __launch_bounds__(kBlock) void conv3d_region_kernel(
 template <int MODE, int CI, int CO, int RB, int QM = 0>
 void launch_mode(const float* x, const float* x2, const float* w, float* y, const float* sc, const float* sh,
                  const float* mu, int B, const Geo& g, hipStream_t s) {
-  const int classes = MODE == kT2 ? 8 : 1;
-  // rows of the largest class (T2) or of the region
-  const int rz = MODE == kT2 ? (g.on[0] + 1) / 2 : g.on[0], ry = MODE == kT2 ? (g.on[1] + 1) / 2 : g.on[1],
-            rx = MODE == kT2 ? (g.on[2] + 1) / 2 : g.on[2];
-  const int rows = rz * ry * rx;
-  const int per_block = (kBlock / 64) * 16 * RB;
-  const int blocks = (rows + per_block - 1) / per_block;
-  const dim3 grid((unsigned)((blocks + 7) / 8 * 8), (unsigned)classes, (unsigned)B);   // XCD remap: multiple of 8
-  hipLaunchKernelGGL((conv3d_region_kernel<MODE, CI, CO, RB, QM>), grid, dim3(kBlock), 0, s, x, x2, w, y, sc, sh, mu,
-                     g);
+  hipLaunchKernelGGL((conv3d_region_kernel<MODE, CI, CO, RB, QM>), region_grid(MODE, RB, B, g.on), dim3(kBlock), 0, s,
+                     x, x2, w, y, sc, sh, mu, g);
 }
 
-// ---- stride-1 convolutions with LDS-staged operands (conv_k_1, model.py:104-113) ----
+// ---- stride-1 convolutions with LDS-staged operands (conv_k_1) ----
 // The per-lane kernel above fetches each input voxel once per tap through L1 / L2 (27 times) and keeps
 // at most RB row blocks of loads in flight: latency-bound (conv_1_1 at ~50 TF/s in the cfg-2 step).
 // Here a workgroup (4 waves) owns a 16 (x) x 4 (y) x TZ (z) block of outputs; its input block, 18 x 6 x
@@ -404,29 +379,29 @@ __global__ __launch_bounds__(kBlock) void conv3d_s1_lds_kernel(
 
   // ---- this wave: column block nb, row blocks rg * 8 .. + 7 of the tile's 4 TZ (z, y) rows ----
   const int nb = wave % NB, rg = wave / NB;
-  f4v_t acc[RB];
+  f4v acc[RB];
 #pragma unroll
-  for (int r = 0; r < RB; ++r) acc[r] = f4v_t{0.0f, 0.0f, 0.0f, 0.0f};
+  for (int r = 0; r < RB; ++r) acc[r] = f4v{0.0f, 0.0f, 0.0f, 0.0f};
   const float* wn = w + (size_t)(nb * 16 + m) * CI + 4 * kq;   // this lane's weight row, channel offset 4 kq
   // A float4s of one (tap, channel block) for the wave's 8 row blocks (buffer tx of three), read one
   // step ahead; the weight float4s of a (tap row, channel block) one iteration ahead
-  f4v_t a[3][RB];
-  auto lda = [&](int tr, int tx, int cb, f4v_t (&dst)[RB]) {
+  f4v a[3][RB];
+  auto lda = [&](int tr, int tx, int cb, f4v (&dst)[RB]) {
     const int tz = tr / 3, ty = tr % 3;
 #pragma unroll
     for (int r = 0; r < RB; ++r) {
       const int rbi = rg * RB + r, zz = rbi >> 2, yy = rbi & 3;
       const int v = ((zz + tz) * T::PY + (yy + ty)) * T::PX + (m + tx);
-      dst[r] = *reinterpret_cast<const f4v_t*>(lds + s1f_off<CI>(v, cb * 4 + kq));
+      dst[r] = *reinterpret_cast<const f4v*>(lds + s1f_off<CI>(v, cb * 4 + kq));
     }
   };
-  auto ldw = [&](int tr, int cb, f4v_t (&bw)[3]) {
+  auto ldw = [&](int tr, int cb, f4v (&bw)[3]) {
 #pragma unroll
     for (int tx = 0; tx < 3; ++tx)
-      bw[tx] = *reinterpret_cast<const f4v_t*>(wn + (size_t)((tr * 3 + tx) * CO) * CI + cb * 16);
+      bw[tx] = *reinterpret_cast<const f4v*>(wn + (size_t)((tr * 3 + tx) * CO) * CI + cb * 16);
   };
   constexpr int CB = CI / 16, NIT = 9 * CB;   // iterations (tap row, channel block)
-  f4v_t bw[3], bn_[3];
+  f4v bw[3], bn_[3];
   ldw(0, 0, bw);
   lda(0, 0, 0, a[0]);
 #pragma unroll 1
@@ -474,9 +449,8 @@ template <int CI>
 void launch_s1_lds(const float* x, const float* w, float* y, const float* sc, const float* sh, const float* mu,
                    int B, const Geo& g, hipStream_t s) {
   const int tx = (g.on[2] + 15) / 16, ty = (g.on[1] + 3) / 4, tz = (g.on[0] + S1TileF<CI>::TZ - 1) / S1TileF<CI>::TZ;
-  const int per = tx * ty * tz;
-  const dim3 grid((unsigned)((per + 7) / 8 * 8), (unsigned)B);   // XCD remap: multiple of 8
-  hipLaunchKernelGGL((conv3d_s1_lds_kernel<CI, CI>), grid, dim3(kBlock), 0, s, x, w, y, sc, sh, mu, g, tx, ty, tz);
+  hipLaunchKernelGGL((conv3d_s1_lds_kernel<CI, CI>), tile_grid(tx * ty * tz, B), dim3(kBlock), 0, s, x, w, y, sc, sh,
+                     mu, g, tx, ty, tz);
 }
 
 }  // namespace

@@ -1,8 +1,8 @@
-// conv3d_region_split.hip -- the regulariser's stride-1 convolutions (conv_k_1, model.py:79-85,
-// forward at model.py:104-113) and stride-2 transposed convolutions (deconv_3_0 / deconv_2_0,
-// model.py:86-88, forward at model.py:117-120) on the f16 matrix cores with split operands, eval BN +
-// ReLU fused.  Same GEMM mapping, region geometry, tap order and epilogue as conv3d_region.hip (whose
-// fp32-MFMA kernel it replaces on the split-fp16 eval path); only the arithmetic differs:
+// conv3d_region_split.hip -- the regulariser's stride-1 convolutions (conv_k_1) and stride-2 transposed
+// convolutions (deconv_3_0 / deconv_2_0; CostVolumeReg, regulariser.py -- the reference's model.py:76-121)
+// on the f16 matrix cores with split operands, eval BN + ReLU fused.  Same GEMM mapping, region geometry,
+// tap order and epilogue as conv3d_region.hip (whose fp32-MFMA kernel it replaces on the split-fp16 eval
+// path; the shared pieces: region_conv.h); only the arithmetic differs:
 //
 //   * operands are split as in split.h: an activation v (fp32, channels-last region tensor, or the sum
 //     of two for `y3 + y2`) is scaled by 2^ex and carried as hi = fp16(v 2^ex), lo = fp16(v 2^ex - hi),
@@ -26,15 +26,10 @@
 #include <cstdlib>
 
 #include "launchers.h"
-#include "packed.h"
-#include "split.h"
+#include "region_conv.h"
 
 namespace mvs {
 namespace {
-
-typedef _Float16 h8v __attribute__((ext_vector_type(8)));
-constexpr uint32_t kOob = 0xFFFFFFC0u;   // out-of-range buffer offset (loads return 0); +16 stays out
-constexpr int kS1 = 0, kS2 = 1, kT2 = 2;
 
 struct GeoS {
   int n[3];    // volume dims
@@ -100,11 +95,6 @@ __device__ inline void stats_write(double (&s)[NB], double (&q)[NB], int nb0, in
   }
 }
 
-__device__ inline void class_dim_s(int o0, int on, int p, int par, int& first, int& cnt) {
-  first = o0 + (((o0 + p) & 1) != par ? 1 : 0);
-  cnt = first < o0 + on ? (o0 + on - 1 - first) / 2 + 1 : 0;
-}
-
 template <int MODE, int CI, int CO, int RB>
 __global__ __launch_bounds__(kBlock) void conv3d_region_split_kernel(
     const float* __restrict__ x, const float* __restrict__ x2, const h8v* __restrict__ wf, int w_exp,
@@ -128,7 +118,7 @@ __global__ __launch_bounds__(kBlock) void conv3d_region_split_kernel(
     par[1] = (cls >> 1) & 1;
     par[2] = cls & 1;
 #pragma unroll
-    for (int d = 0; d < 3; ++d) class_dim_s(g.o0[d], g.on[d], g.pad[d], par[d], cf[d], cn[d]);
+    for (int d = 0; d < 3; ++d) class_dim(g.o0[d], g.on[d], g.pad[d], par[d], cf[d], cn[d]);
   } else {
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
@@ -258,18 +248,14 @@ __global__ __launch_bounds__(kBlock) void conv3d_region_split_kernel(
         bhi[nb] = blds[kb & 1][(nb * 2 + 0) * 64 + lane];
         blo[nb] = blds[kb & 1][(nb * 2 + 1) * 64 + lane];
       } else {
-        bhi[nb] = wf[((size_t)(kb * NB + nb) * 2 + 0) * 64 + lane];
-        blo[nb] = wf[((size_t)(kb * NB + nb) * 2 + 1) * 64 + lane];
+        bhi[nb] = wfrag(wf, kb, NB, nb, 0, lane);
+        blo[nb] = wfrag(wf, kb, NB, nb, 1, lane);
       }
     }
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
-      for (int nb = 0; nb < NB; ++nb) {
-        acc[rb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi[rb], bhi[nb], acc[rb][nb], 0, 0, 0);
-        acc[rb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi[rb], blo[nb], acc[rb][nb], 0, 0, 0);
-        acc[rb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo[rb], bhi[nb], acc[rb][nb], 0, 0, 0);
-      }
+      for (int nb = 0; nb < NB; ++nb) mfma3(ahi[rb], alo[rb], bhi[nb], blo[nb], acc[rb][nb]);
     if constexpr (BL) {
       constexpr int NK = 27 * CB;   // one K block per (tap, 32 channels)
       if (kb + 1 < NK) bstore((kb + 1) & 1);
@@ -368,27 +354,15 @@ __global__ __launch_bounds__(kBlock) void conv3d_region_split_kernel(
   }
 }
 
-// the per-lane kernel's grid: (row chunks of a parity class, rounded to the 8 XCDs) x classes x batch
-inline dim3 split_mode_grid(int mode, int RB, int B, const int* on) {
-  const int classes = mode == kT2 ? 8 : 1;
-  const int rz = mode == kT2 ? (on[0] + 1) / 2 : on[0], ry = mode == kT2 ? (on[1] + 1) / 2 : on[1],
-            rx = mode == kT2 ? (on[2] + 1) / 2 : on[2];
-  const long rows = (long)rz * ry * rx;
-  const long per_block = (kBlock / 64) * 16 * RB;
-  const long blocks = (rows + per_block - 1) / per_block;
-  return dim3((unsigned)((blocks + 7) / 8 * 8), (unsigned)classes, (unsigned)B);
-}
-
 template <int MODE, int CI, int CO, int RB>
 void launch_split_mode(const float* x, const float* x2, const void* wf, int w_exp, float* y, const float* sc,
                        const float* sh, const float* mu, int B, const GeoS& g, const uint32_t* xb,
                        const uint32_t* xb2, uint32_t* yb, hipStream_t s) {
-  const dim3 grid = split_mode_grid(MODE, RB, B, g.on);
-  hipLaunchKernelGGL((conv3d_region_split_kernel<MODE, CI, CO, RB>), grid, dim3(kBlock), 0, s, x, x2,
-                     reinterpret_cast<const h8v*>(wf), w_exp, y, sc, sh, mu, g, xb, xb2, yb);
+  hipLaunchKernelGGL((conv3d_region_split_kernel<MODE, CI, CO, RB>), region_grid(MODE, RB, B, g.on), dim3(kBlock), 0, s,
+                     x, x2, reinterpret_cast<const h8v*>(wf), w_exp, y, sc, sh, mu, g, xb, xb2, yb);
 }
 
-// ---- stride-1 convolutions with LDS-staged operands (conv_k_1; model.py:104-113) ----
+// ---- stride-1 convolutions with LDS-staged operands (conv_k_1) ----
 // The per-lane kernel above fetches every input voxel once per tap through L1 (27x): for the
 // 16-channel conv_1_1 that operand traffic, not the MFMA, sets its time.  Here a workgroup (4 waves)
 // owns a 16 (x) x 4 (y) x TZ (z) block of outputs; its input block, 18 x 6 x (TZ + 2) voxels with
@@ -399,19 +373,11 @@ void launch_split_mode(const float* x, const float* x2, const void* wf, int w_ex
 // (global / L2) feeds 8 row blocks, every A fragment comes from LDS.  Same products, same K order as
 // the per-lane kernel (taps, then channel blocks; tap pairs for CI = 16): bit-equal outputs.
 template <int CI>
-struct S1Tile {
+struct S1Tile : SplitRec<CI> {
   static constexpr int TZ = CI == 16 ? 8 : (CI == 32 ? 4 : 2);
   static constexpr int PX = 18, PY = 6, PZ = TZ + 2, PV = PX * PY * PZ;
-  static constexpr int REC = CI * 4;     // bytes per voxel record (CI hi + CI lo fp16)
-  static constexpr int NCH = REC / 16;   // 16-byte chunks per record: 4, 8, 16
-  static constexpr int LDS = PV * REC;   // 69,120 / 82,944 / 110,592 B
+  static constexpr int LDS = PV * SplitRec<CI>::REC;   // 69,120 / 82,944 / 110,592 B
 };
-
-template <int CI>
-__device__ inline int s1_chunk_off(int v, int c) {
-  using T = S1Tile<CI>;
-  return v * T::REC + ((c ^ ((v / (16 / T::NCH)) % T::NCH)) << 4);
-}
 
 template <int CI, int CO>
 __global__ __launch_bounds__(kBlock) void conv3d_s1_split_lds_kernel(
@@ -498,8 +464,8 @@ __global__ __launch_bounds__(kBlock) void conv3d_s1_split_lds_kernel(
           for (int jj = 0; jj < 4; ++jj) a[jj] = fmaxf((a[jj] - bmu[jj]) * bsc[jj] + bsh[jj], 0.0f);
         }
         split4(a, ex, hi, lo);
-        *reinterpret_cast<uint2*>(lds + s1_chunk_off<CI>(v, q >> 1) + ((q & 1) << 3)) = hi;
-        *reinterpret_cast<uint2*>(lds + s1_chunk_off<CI>(v, CI / 8 + (q >> 1)) + ((q & 1) << 3)) = lo;
+        *reinterpret_cast<uint2*>(lds + T::chunk_off(v, q >> 1) + ((q & 1) << 3)) = hi;
+        *reinterpret_cast<uint2*>(lds + T::chunk_off(v, CI / 8 + (q >> 1)) + ((q & 1) << 3)) = lo;
       }
     }
   }
@@ -512,8 +478,8 @@ __global__ __launch_bounds__(kBlock) void conv3d_s1_split_lds_kernel(
   for (int r = 0; r < RB; ++r) acc[r] = f4v{0.0f, 0.0f, 0.0f, 0.0f};
   // weight fragments (L2) one K block ahead: kb + 1's loads are in flight under kb's MFMAs
   auto ldb = [&](int kb, h8v& bhi, h8v& blo) {
-    bhi = wf[((size_t)(kb * NB + nb) * 2 + 0) * 64 + lane];
-    blo = wf[((size_t)(kb * NB + nb) * 2 + 1) * 64 + lane];
+    bhi = wfrag(wf, kb, NB, nb, 0, lane);
+    blo = wfrag(wf, kb, NB, nb, 1, lane);
   };
   auto kstep = [&](int kb, const h8v& bhi, const h8v& blo) {
     int tap, c0;
@@ -530,9 +496,10 @@ __global__ __launch_bounds__(kBlock) void conv3d_s1_split_lds_kernel(
     for (int r = 0; r < RB; ++r) {
       const int rbi = rg * RB + r, zz = rbi >> 2, yy = rbi & 3;
       const int v = ((zz + tz) * T::PY + (yy + ty)) * T::PX + (m + tx);
-      h8v ahi = *reinterpret_cast<const h8v*>(lds + s1_chunk_off<CI>(v, c0));
-      h8v alo = *reinterpret_cast<const h8v*>(lds + s1_chunk_off<CI>(v, CI / 8 + c0));
+      h8v ahi = *reinterpret_cast<const h8v*>(lds + T::chunk_off(v, c0));
+      h8v alo = *reinterpret_cast<const h8v*>(lds + T::chunk_off(v, CI / 8 + c0));
       if (!tap_ok) ahi = alo = h8v{0, 0, 0, 0, 0, 0, 0, 0};
+      // (mfma3's products written out: through the helper the 16-channel form's instruction stream changes)
       acc[r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, bhi, acc[r], 0, 0, 0);
       acc[r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, blo, acc[r], 0, 0, 0);
       acc[r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, bhi, acc[r], 0, 0, 0);
@@ -600,14 +567,12 @@ void launch_s1_lds(const float* x, const void* wf, int w_exp, float* y, const fl
                    const float* mu, int B, const GeoS& g, const uint32_t* xb, uint32_t* yb, hipStream_t s) {
   int tx, ty, tz;
   s1_lds_tiles<CI>(g.on, tx, ty, tz);
-  const int per = tx * ty * tz;
-  const dim3 grid((unsigned)((per + 7) / 8 * 8), (unsigned)B);
-  hipLaunchKernelGGL((conv3d_s1_split_lds_kernel<CI, CI>), grid, dim3(kBlock), 0, s, x,
+  hipLaunchKernelGGL((conv3d_s1_split_lds_kernel<CI, CI>), tile_grid(tx * ty * tz, B), dim3(kBlock), 0, s, x,
                      reinterpret_cast<const h8v*>(wf), w_exp, y, sc, sh, mu, g, tx, ty, tz, xb, yb);
 }
 
 // ---- transposed convolutions over large output regions with LDS-staged operands (train mode's
-// deconv_3_0 / deconv_2_0 over the full volume, model.py:117-120) ----
+// deconv_3_0 / deconv_2_0 over the full volume) ----
 // A workgroup owns a TX x 8 x 4 block of outputs of ALL eight parity classes; every output of it reads
 // inputs i = (o + P - t) / 2 from one (TX / 2 + 1) x 5 x 3 input block, which is loaded once, split and
 // stored in LDS as S1Tile's swizzled records (the per-lane kernel re-reads each input voxel through
@@ -625,12 +590,10 @@ void launch_s1_lds(const float* x, const void* wf, int w_exp, float* y, const fl
 #define MVS_T2_TYB 1
 #endif
 template <int CI, int TXB, int TYB = MVS_T2_TYB>
-struct T2Tile {
+struct T2Tile : SplitRec<CI> {
   static constexpr int TX = 32 * TXB, TY = 8 * TYB, TZ = 4;
   static constexpr int PX = TX / 2 + 1, PY = TY / 2 + 1, PZ = TZ / 2 + 1, PV = PX * PY * PZ;
-  static constexpr int REC = CI * 4, NCH = REC / 16;
-  static constexpr int LDS = PV * REC;
-  __device__ static int chunk_off(int v, int c) { return v * REC + ((c ^ ((v / (16 / NCH)) % NCH)) << 4); }
+  static constexpr int LDS = PV * SplitRec<CI>::REC;
 };
 
 template <int CI, int CO, int TXB>
@@ -749,8 +712,8 @@ __global__ __launch_bounds__(kBlock) void conv3d_t2_split_lds_kernel(
   auto ldb = [&](int kb, h8v (&bh)[NB], h8v (&bl)[NB]) {
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
-      bh[nb] = wf[((size_t)(kb * NB + nb) * 2 + 0) * 64 + lane];
-      bl[nb] = wf[((size_t)(kb * NB + nb) * 2 + 1) * 64 + lane];
+      bh[nb] = wfrag(wf, kb, NB, nb, 0, lane);
+      bl[nb] = wfrag(wf, kb, NB, nb, 1, lane);
     }
   };
 
@@ -794,11 +757,7 @@ __global__ __launch_bounds__(kBlock) void conv3d_t2_split_lds_kernel(
         const h8v ahi = *reinterpret_cast<const h8v*>(lds + T::chunk_off(v, c0));
         const h8v alo = *reinterpret_cast<const h8v*>(lds + T::chunk_off(v, CI / 8 + c0));
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-          acc[r][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, bh[nb], acc[r][nb], 0, 0, 0);
-          acc[r][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, bl[nb], acc[r][nb], 0, 0, 0);
-          acc[r][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, bh[nb], acc[r][nb], 0, 0, 0);
-        }
+        for (int nb = 0; nb < NB; ++nb) mfma3(ahi, alo, bh[nb], bl[nb], acc[r][nb]);
       }
     };
     h8v bh0[NB], bl0[NB], bh1[NB], bl1[NB];
@@ -878,9 +837,7 @@ void launch_t2_lds(const float* x, const float* x2, const void* wf, int w_exp, f
                    uint32_t* yb, hipStream_t s) {
   int tx, ty, tz;
   t2_lds_tiles<CI, TXB>(g.on, tx, ty, tz);
-  const int per = tx * ty * tz;
-  const dim3 grid((unsigned)((per + 7) / 8 * 8), (unsigned)B);
-  hipLaunchKernelGGL((conv3d_t2_split_lds_kernel<CI, CO, TXB>), grid, dim3(kBlock), 0, s, x, x2,
+  hipLaunchKernelGGL((conv3d_t2_split_lds_kernel<CI, CO, TXB>), tile_grid(tx * ty * tz, B), dim3(kBlock), 0, s, x, x2,
                      reinterpret_cast<const h8v*>(wf), w_exp, y, sc, sh, mu, g, tx, ty, tz, xb, xb2, yb);
 }
 
@@ -952,7 +909,7 @@ long conv3d_region_split_slots(int mode, int B, int CI, int CO, const int* on, b
     else s1_lds_tiles<64>(on, tx, ty, tz);
     return (long)B * tx * ty * tz;
   }
-  const dim3 gr = split_mode_grid(mode, split_rb(mode, B, on, CO), B, on);
+  const dim3 gr = region_grid(mode, split_rb(mode, B, on, CO), B, on);
   return (long)gr.x * gr.y * gr.z;
 }
 
