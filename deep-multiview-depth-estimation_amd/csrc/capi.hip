@@ -658,6 +658,54 @@ int mvs_conv3d_region_wgrad(const float* x, const float* gy, int batch, int chan
   return lc.status();
 }
 
+namespace {
+// MVS_OK when mvs_conv3d_s2_region_wgrad / _dgrad can launch on this geometry
+int s2_region_bwd_geometry(int batch, const int* dims, const int* pad_lo, const int* out_size) {
+  if (!dims || !out_size || batch <= 0) return MVS_ERR_INVALID_ARGUMENT;
+  uint64_t vox = (uint64_t)batch, ovox = (uint64_t)batch, osample = 1;
+  for (int k = 0; k < 3; ++k)
+    if (dims[k] < 1 || out_size[k] < 1 || (pad_lo && pad_lo[k] < 0)) return MVS_ERR_INVALID_ARGUMENT;
+  for (int k = 0; k < 3; ++k) {
+    vox *= (uint64_t)dims[k];
+    ovox *= (uint64_t)out_size[k];
+    osample *= (uint64_t)out_size[k];
+    if (vox >= (1ull << 31) || ovox >= (1ull << 31)) return MVS_ERR_TOO_LARGE;   // 32-bit row and voxel indices
+    if (pad_lo && pad_lo[k] >= (1 << 29)) return MVS_ERR_TOO_LARGE;               // 2 o - pad_lo + t in 32 bits
+  }
+  // one sample of gy behind one 32-bit buffer descriptor (the input gradient's loads)
+  if (osample * 112u * sizeof(float) >= 0xFFFFFFC0ull) return MVS_ERR_TOO_LARGE;
+  return MVS_OK;
+}
+}  // namespace
+
+size_t mvs_conv3d_s2_region_wgrad_workspace_bytes(int batch, const int* dims, const int* out_size) {
+  if (s2_region_bwd_geometry(batch, dims, nullptr, out_size) != MVS_OK) return 0;
+  return mvs::conv3d_s2_wgrad_workspace_bytes(batch, dims, out_size);
+}
+
+int mvs_conv3d_s2_region_wgrad(const float* x, const float* gy, int batch, const int* dims, const int* pad_lo,
+                               const int* out_size, float* dw, float* workspace, void* stream) {
+  if (!x || !gy || !dw || !workspace || !pad_lo) return MVS_ERR_INVALID_ARGUMENT;
+  if (((uintptr_t)x | (uintptr_t)gy | (uintptr_t)dw | (uintptr_t)workspace) & 15u) return MVS_ERR_INVALID_ARGUMENT;
+  const int st = s2_region_bwd_geometry(batch, dims, pad_lo, out_size);
+  if (st != MVS_OK) return st;
+  const mvs::LaunchCheck lc;
+  mvs::launch_conv3d_s2_wgrad(x, gy, batch, dims, pad_lo, out_size, workspace, dw, (hipStream_t)stream);
+  return lc.status();
+}
+
+int mvs_conv3d_s2_region_dgrad(const float* gy, const float* w27, int batch, const int* dims, const int* pad_lo,
+                               const int* out_size, float* gx, void* stream) {
+  if (!gy || !w27 || !gx || !pad_lo) return MVS_ERR_INVALID_ARGUMENT;
+  if (((uintptr_t)gy | (uintptr_t)w27 | (uintptr_t)gx) & 15u) return MVS_ERR_INVALID_ARGUMENT;
+  const int st = s2_region_bwd_geometry(batch, dims, pad_lo, out_size);
+  if (st != MVS_OK) return st;
+  if (batch > 65535) return MVS_ERR_TOO_LARGE;   // grid.z
+  const mvs::LaunchCheck lc;
+  mvs::launch_conv3d_s2_dgrad(gy, w27, gx, batch, dims, pad_lo, out_size, (hipStream_t)stream);
+  return lc.status();
+}
+
 int mvs_conv_head_fp32_fwd(const float* cv4, int batch, int d, int h, int w, const float* w0_wz,
                            const float* bn0_scale, const float* bn0_shift, const float* bn0_mean, const float* w1,
                            const float* w1_pass, const float* bn1_scale, const float* bn1_shift,

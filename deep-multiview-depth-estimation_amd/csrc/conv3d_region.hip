@@ -63,7 +63,11 @@ __device__ inline void store_out(float* __restrict__ y, const Geo& g, int b, int
 // CLS (T2 only): the parity class (pz, py, px) = bits (2, 1, 0) as a COMPILE-TIME constant, so the tap
 // loops unroll to exactly the class's 1-8 taps in one basic block (the loads of every tap issued ahead of
 // the MFMAs); the kernel below dispatches on blockIdx.y.  -1 (S1 / S2): no classes.
-template <int MODE, int CI, int CO, int RB, int QM, int CLS>
+// PS: independent partial sums per output.  1: one accumulation chain over every (tap, channel) -- every
+// forward instantiation.  4 (CI = 112, the stacked stride-2 layers' input gradient): one chain per channel
+// group (16 | 32 | 32 | 32: conv_1_0, conv_2_0 and the halves of conv_3_0), added once in the epilogue as
+// (p0 + p1) + (p2 + p3) -- a chain is at most 8 taps x 32 channels long instead of 8 x 112.
+template <int MODE, int CI, int CO, int RB, int QM, int CLS, int PS = 1>
 __device__ __forceinline__ void region_conv(
     const float* __restrict__ x, const float* __restrict__ x2, const float* __restrict__ w,
     float* __restrict__ y, const float* __restrict__ bn_scale, const float* __restrict__ bn_shift,
@@ -71,6 +75,7 @@ __device__ __forceinline__ void region_conv(
   constexpr int NB = CO / 16;          // column blocks
   static_assert(CI % 16 == 0 && CO % 16 == 0, "channel counts in multiples of 16");
   static_assert((MODE == kT2) == (CLS >= 0), "parity classes: transposed convolutions");
+  static_assert(PS == 1 || (PS == 4 && CI == 112), "partial sums: the 112-channel input gradient only");
   const int lane = (int)threadIdx.x & 63;
   const int m = lane & 15, kq = lane >> 4;   // MFMA row / K index of this lane's A value
   const int b = (int)blockIdx.z;
@@ -135,11 +140,13 @@ __device__ __forceinline__ void region_conv(
     lin[rb] = (bs[0] * lim[1] + bs[1]) * lim[2] + bs[2];
   }
 
-  f4v acc[RB][NB];
+  f4v acc[PS][RB][NB];
 #pragma unroll
-  for (int rb = 0; rb < RB; ++rb)
+  for (int ps = 0; ps < PS; ++ps)
 #pragma unroll
-    for (int nb = 0; nb < NB; ++nb) acc[rb][nb] = f4v{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) acc[ps][rb][nb] = f4v{0.0f, 0.0f, 0.0f, 0.0f};
 
   // buffer descriptors (workgroup-uniform bases; out-of-range offsets read 0): S2 the sample's
   // volume (channel-quad: quads cb*4 .. cb*4+3 per channel block; NCDHW: 16 channel planes per
@@ -173,6 +180,7 @@ __device__ __forceinline__ void region_conv(
 #pragma unroll
       for (int cb = 0; cb < CI / 16; ++cb) {
         const int c4 = cb * 16 + kq * 4;
+        const int ps = PS == 1 ? 0 : (cb + 1) / 2;   // this channel block's partial sum
         Rsrc rs, rs2;
         if constexpr (MODE == kS2) {
           if constexpr (QM == 2)   // bf16 quads: 8 bytes per voxel and quad
@@ -234,7 +242,8 @@ __device__ __forceinline__ void region_conv(
             for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
               for (int nb = 0; nb < NB; ++nb)
-                acc[rb][nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[tx][rb][s], bw[tx][nb][s], acc[rb][nb], 0, 0, 0);
+                acc[ps][rb][nb] =
+                    __builtin_amdgcn_mfma_f32_16x16x4f32(a[tx][rb][s], bw[tx][nb][s], acc[ps][rb][nb], 0, 0, 0);
         }
       }
     }
@@ -257,7 +266,9 @@ __device__ __forceinline__ void region_conv(
         const int jy = t % cn[1], jz = t / cn[1];
         const int vz = cf[0] + step * jz - g.o0[0], vy = cf[1] + step * jy - g.o0[1],
                   vx = cf[2] + step * jx - g.o0[2];
-        float v = acc[rb][nb][r];
+        float v = acc[0][rb][nb][r];
+        if constexpr (PS == 4)
+          v = (v + acc[1][rb][nb][r]) + (acc[PS - 2][rb][nb][r] + acc[PS - 1][rb][nb][r]);
         if (bn_scale) v = fmaxf((v - mu) * sc + sh, 0.0f);
         vmax = fmaxf(vmax, fabsf(v));
         store_out(y, g, b, co, vz, vy, vx, CO, v);
@@ -266,7 +277,7 @@ __device__ __forceinline__ void region_conv(
   if (g.y_bound) bound_update(g.y_bound, vmax);
 }
 
-template <int MODE, int CI, int CO, int RB, int QM = 0>
+template <int MODE, int CI, int CO, int RB, int QM = 0, int PS = 1>
 __global__ __launch_bounds__(kBlock) void conv3d_region_kernel(
     const float* __restrict__ x, const float* __restrict__ x2, const float* __restrict__ w,
     float* __restrict__ y, const float* __restrict__ bn_scale, const float* __restrict__ bn_shift,
@@ -274,21 +285,21 @@ __global__ __launch_bounds__(kBlock) void conv3d_region_kernel(
   if constexpr (MODE == kT2) {
     switch (blockIdx.y) {   // workgroup-uniform
 #define MVS_T2_CLASS(c) \
-  case c: region_conv<MODE, CI, CO, RB, QM, c>(x, x2, w, y, bn_scale, bn_shift, bn_mean, g); break;
+  case c: region_conv<MODE, CI, CO, RB, QM, c, PS>(x, x2, w, y, bn_scale, bn_shift, bn_mean, g); break;
       MVS_T2_CLASS(0) MVS_T2_CLASS(1) MVS_T2_CLASS(2) MVS_T2_CLASS(3)
       MVS_T2_CLASS(4) MVS_T2_CLASS(5) MVS_T2_CLASS(6) MVS_T2_CLASS(7)
 #undef MVS_T2_CLASS
       default: break;
     }
   } else {
-    region_conv<MODE, CI, CO, RB, QM, -1>(x, x2, w, y, bn_scale, bn_shift, bn_mean, g);
+    region_conv<MODE, CI, CO, RB, QM, -1, PS>(x, x2, w, y, bn_scale, bn_shift, bn_mean, g);
   }
 }
 
-template <int MODE, int CI, int CO, int RB, int QM = 0>
+template <int MODE, int CI, int CO, int RB, int QM = 0, int PS = 1>
 void launch_mode(const float* x, const float* x2, const float* w, float* y, const float* sc, const float* sh,
                  const float* mu, int B, const Geo& g, hipStream_t s) {
-  hipLaunchKernelGGL((conv3d_region_kernel<MODE, CI, CO, RB, QM>), region_grid(MODE, RB, B, g.on), dim3(kBlock), 0, s,
+  hipLaunchKernelGGL((conv3d_region_kernel<MODE, CI, CO, RB, QM, PS>), region_grid(MODE, RB, B, g.on), dim3(kBlock), 0, s,
                      x, x2, w, y, sc, sh, mu, g);
 }
 
@@ -538,6 +549,30 @@ int launch_conv3d_region(int mode, bool out_cf, int in_c4, const float* x, const
 #undef MVS_REGION_CASE
 #undef MVS_REGION_S2
   return MVS_ERR_INVALID_ARGUMENT;
+}
+
+// Input gradient of the stacked stride-2 convolution (conv_1_0 / conv_2_0 / conv_3_0: 32 -> 112 on the output
+// box `out` of the whole volume n): gx[b][ci][i] = sum over taps t and co of gy[b][(i + pad_lo - t) / 2][co]
+// w[co][ci][t] -- the transposed mode with gy (channels-last, 112 channels) as the input region at origin 0,
+// the whole volume as the output region, written NCDHW, w27 [27][32][112], four partial sums per output.
+void launch_conv3d_s2_dgrad(const float* gy, const float* w27, float* gx, int B, const int* n, const int* pad_lo,
+                            const int* out, hipStream_t s) {
+  Geo g;
+  g.y_bound = nullptr;
+  g.absmax = nullptr;
+  g.out_cf = 1;
+  g.in_c4 = 0;
+  for (int d = 0; d < 3; ++d) {
+    g.n[d] = n[d];
+    g.o0[d] = 0;
+    g.on[d] = n[d];
+    g.i0[d] = 0;
+    g.in[d] = out[d];
+    g.pad[d] = pad_lo[d];
+    g.st0[d] = 0;
+    g.stn[d] = n[d];
+  }
+  launch_mode<kT2, 112, 32, 2, 0, 4>(gy, nullptr, w27, gx, nullptr, nullptr, nullptr, B, g, s);
 }
 
 }  // namespace mvs

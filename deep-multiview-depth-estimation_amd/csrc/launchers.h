@@ -101,6 +101,16 @@ bool conv3d_region_wgrad_supported(int C);
 size_t conv3d_region_wgrad_workspace_bytes(int B, int C, const int* L);
 void launch_conv3d_region_wgrad(const float* x, const float* gy, int B, int C, const int* L, float* part, float* dw,
                                 hipStream_t s);
+// csrc/conv3d_s2_wgrad.hip: weight gradient of the stacked stride-2 region convolution 32 -> 112 (x NCDHW
+// [B][32][n...] read in place, gy channels-last [B][out...][112], output o reads inputs 2 o - pad_lo + t;
+// dw [112][32][27]); part: the workspace
+size_t conv3d_s2_wgrad_workspace_bytes(int B, const int* n, const int* out);
+void launch_conv3d_s2_wgrad(const float* x, const float* gy, int B, const int* n, const int* pad_lo, const int* out,
+                            float* part, float* dw, hipStream_t s);
+// csrc/conv3d_region.hip: its input gradient gx NCDHW [B][32][n...] from gy and w27 [27][32][112] (the
+// transposed mode, four partial sums per output)
+void launch_conv3d_s2_dgrad(const float* gy, const float* w27, float* gx, int B, const int* n, const int* pad_lo,
+                            const int* out, hipStream_t s);
 void launch_conv3d_k3_narrow(const float* in, int in_c4, bool wino_z, const float* weight, float* out, int B,
                              int Cin, int Cout, int D, int H, int W, const float* bn_scale, const float* bn_shift,
                              const float* bn_mean, hipStream_t s, const float* in2 = nullptr,

@@ -112,6 +112,9 @@ TRAIN_SIGNATURES = {
     "mvs_train_abi_version": (_c_int, []),
     "mvs_conv3d_region_wgrad_workspace_bytes": (ctypes.c_size_t, [_c_int, _c_int, _p]),
     "mvs_conv3d_region_wgrad": (_c_int, [_p, _p, _c_int, _c_int, _p, _p, _p, _p]),
+    "mvs_conv3d_s2_region_wgrad_workspace_bytes": (ctypes.c_size_t, [_c_int, _p, _p]),
+    "mvs_conv3d_s2_region_wgrad": (_c_int, [_p, _p, _c_int, _p, _p, _p, _p, _p, _p]),
+    "mvs_conv3d_s2_region_dgrad": (_c_int, [_p, _p, _c_int, _p, _p, _p, _p, _p]),
 }
 
 

@@ -763,6 +763,77 @@ def conv3d_region_wgrad(x_cl: torch.Tensor, gy_cl: torch.Tensor) -> torch.Tensor
     return dw
 
 
+S2_BWD_CHANNELS = (32, 112)   # (c_in, c_out) of mvs_conv3d_s2_region_wgrad / _dgrad: conv_1_0 | conv_2_0 | conv_3_0
+
+
+def _pad3(pad_lo):
+    pad_lo = tuple(int(p) for p in pad_lo)
+    if len(pad_lo) != 3 or min(pad_lo) < 0:
+        raise ValueError("pad_lo: three ints >= 0 expected, got %s" % (pad_lo,))
+    return pad_lo
+
+
+def conv3d_s2_region_wgrad(x: torch.Tensor, gy_cl: torch.Tensor, pad_lo) -> torch.Tensor:
+    """Weight gradient of the stacked stride-2 region convolution nn.Conv3d(32, 112, 3, stride=2, bias=False)
+    (model.py:101-107 conv_1_0 / conv_2_0 / conv_3_0 on an output box: output o reads inputs 2 o - pad_lo + t)
+    from its NCDHW input x [B, 32, D, H, W] (read in place: no channels-last copy) and channels-last output
+    gradient gy_cl [B, Oz, Oy, Ox, 112]: dw [112, 32, 3, 3, 3] on the f32 matrix cores
+    (mvs_conv3d_s2_region_wgrad of the training extension, deterministic)."""
+    _require_gpu(x, "x")
+    _require_gpu(gy_cl, "gy_cl")
+    lib = _lib.load()
+    cin, cout = S2_BWD_CHANNELS
+    if (x.dim() != 5 or gy_cl.dim() != 5 or x.shape[0] != gy_cl.shape[0] or x.shape[1] != cin
+            or gy_cl.shape[4] != cout):
+        raise ValueError("x [B, %d, D, H, W] and gy_cl [B, Oz, Oy, Ox, %d] expected, got %s and %s"
+                         % (cin, cout, tuple(x.shape), tuple(gy_cl.shape)))
+    pad = _ints3(_pad3(pad_lo))
+    b = x.shape[0]
+    x = x.to(_F32).contiguous()
+    gy_cl = gy_cl.to(device=x.device, dtype=_F32).contiguous()
+    dims, out = _ints3(x.shape[2:]), _ints3(gy_cl.shape[1:4])
+    nbytes = lib.mvs_conv3d_s2_region_wgrad_workspace_bytes(b, dims, out)
+    if nbytes == 0:
+        raise ValueError("volume %s, box %s: every extent >= 1 and B * voxels < 2^31 expected"
+                         % (tuple(x.shape[2:]), tuple(gy_cl.shape[1:4])))
+    ws = torch.empty(nbytes // 4, device=x.device, dtype=_F32)
+    dw = torch.empty((cout, cin, 3, 3, 3), device=x.device, dtype=_F32)
+    st = lib.mvs_conv3d_s2_region_wgrad(_lib.ptr(x), _lib.ptr(gy_cl), b, dims, pad, out, _lib.ptr(dw), _lib.ptr(ws),
+                                        _lib.stream_handle(x.device))
+    _lib.check(st, "mvs_conv3d_s2_region_wgrad")
+    return dw
+
+
+def conv3d_s2_region_dgrad(gy_cl: torch.Tensor, w: torch.Tensor, dims, pad_lo) -> torch.Tensor:
+    """Input gradient of the same convolution from gy_cl [B, Oz, Oy, Ox, 112] and its weight w
+    [112, 32, 3, 3, 3]: gx [B, 32, *dims] NCDHW (every element written), gx[b, :, i] = sum over taps t and co
+    of gy[b, (i + pad_lo - t) / 2, co] w[co, :, t] (mvs_conv3d_s2_region_dgrad: the transposed mode of the
+    fp32 region kernel, four partial sums per output)."""
+    _require_gpu(gy_cl, "gy_cl")
+    _require_gpu(w, "w")
+    lib = _lib.load()
+    cin, cout = S2_BWD_CHANNELS
+    dims = tuple(int(d) for d in dims)
+    if gy_cl.dim() != 5 or gy_cl.shape[4] != cout or tuple(w.shape) != (cout, cin, 3, 3, 3):
+        raise ValueError("gy_cl [B, Oz, Oy, Ox, %d] and w [%d, %d, 3, 3, 3] expected, got %s and %s"
+                         % (cout, cout, cin, tuple(gy_cl.shape), tuple(w.shape)))
+    if len(dims) != 3 or min(dims) < 1:
+        raise ValueError("dims: three ints >= 1 expected, got %s" % (dims,))
+    pad = _ints3(_pad3(pad_lo))
+    b = gy_cl.shape[0]
+    gy_cl = gy_cl.to(_F32).contiguous()
+    w27 = w.detach().to(device=gy_cl.device, dtype=_F32).permute(2, 3, 4, 1, 0).reshape(27, cin, cout).contiguous()
+    size, out = _ints3(dims), _ints3(gy_cl.shape[1:4])
+    if lib.mvs_conv3d_s2_region_wgrad_workspace_bytes(b, size, out) == 0:   # (the two share their geometry check)
+        raise ValueError("volume %s, box %s: every extent >= 1 and B * voxels < 2^31 expected"
+                         % (dims, tuple(gy_cl.shape[1:4])))
+    gx = torch.empty((b, cin) + dims, device=gy_cl.device, dtype=_F32)
+    st = lib.mvs_conv3d_s2_region_dgrad(_lib.ptr(gy_cl), _lib.ptr(w27), b, size, pad, out, _lib.ptr(gx),
+                                        _lib.stream_handle(gy_cl.device))
+    _lib.check(st, "mvs_conv3d_s2_region_dgrad")
+    return gx
+
+
 @torch.library.custom_op("mvs::conv_head_fp32", mutates_args=())
 def conv_head_fp32(cv4: torch.Tensor, w0: torch.Tensor, bn0_scale: Optional[torch.Tensor],
                    bn0_shift: Optional[torch.Tensor], bn0_mean: Optional[torch.Tensor], w1: torch.Tensor,

@@ -10,7 +10,10 @@ conv3d_box / conv_transpose3d_box).  The tap GEMMs accumulate every tap's produc
   transposed deconv_3_0 / deconv_2_0 (model.py:117-120, the full box from M)  mode T2
 MVS_TRAIN_REGION_FWD selects which (enabled()).  MVS_TRAIN_REGION_BWD (bwd_enabled(), default "taps") moves
 the stride-1 layers' backward onto HIP kernels as well: the input gradient on the forward's region kernel
-in its adjoint geometry, the weight gradient on csrc/conv3d_region_wgrad.hip."""
+in its adjoint geometry, the weight gradient on csrc/conv3d_region_wgrad.hip.  MVS_TRAIN_S2_BWD
+(s2_bwd_enabled(), default "taps") does the same for the stacked stride-2 layer: the input gradient on the
+region kernel's transposed mode, the weight gradient on csrc/conv3d_s2_wgrad.hip, both from the NCDHW volume
+in place."""
 import os
 
 import torch
@@ -57,27 +60,56 @@ def _cf(t):            # channels-last [B, d, h, w, C] -> logical NCDHW view
     return t.permute(0, 4, 1, 2, 3)
 
 
+def s2_bwd_enabled(x):
+    """The backward of the stacked stride-2 layers (32 -> 16 + 32 + 64) runs on the HIP kernels
+    (ops.conv3d_s2_region_wgrad / conv3d_s2_region_dgrad).  MVS_TRAIN_S2_BWD, read on every call: "hip", or
+    "taps" (the per-tap GEMMs; the default).  A switch of its own: MVS_TRAIN_REGION_BWD never names "s2"."""
+    on = os.environ.get("MVS_TRAIN_S2_BWD", "taps") == "hip"
+    return on and x.is_cuda and x.dtype == torch.float32
+
+
 class _S2Box(torch.autograd.Function):
+    """The stride-2 convolution on its output box.  hip_fwd: the forward on the region kernel (one launch per
+    layer), else tap_gemm.conv3d_box's arithmetic.  hip_bwd (the stacked 32 -> 112 layer only): the backward
+    on ops.conv3d_s2_region_wgrad / conv3d_s2_region_dgrad, else tap_gemm.conv3d_backward.  Both are decided by
+    the caller (s2_box: grad mode is off in here).  Only x and w are saved."""
+
     @staticmethod
-    def forward(ctx, x, w, out_reg, pad, pad_lo, splits):
-        from .ops import CONV_S2, conv3d_region
-        n = list(x.shape[2:])
-        org, size = origin(out_reg), extent(out_reg)
-        xc = x.contiguous()
-        ys, c0 = [], 0
-        for co in splits:
-            ys.append(conv3d_region(xc, None, _region_w(w[c0:c0 + co]), CONV_S2, n, org, size, None, None, list(pad)))
-            c0 += co
+    def forward(ctx, x, w, out_reg, pad, pad_lo, splits, hip_fwd, hip_bwd):
+        size = extent(out_reg)
+        if hip_fwd:
+            from .ops import CONV_S2, conv3d_region
+            n = list(x.shape[2:])
+            org = origin(out_reg)
+            xc = x.contiguous()
+            ys, c0 = [], 0
+            for co in splits:
+                ys.append(conv3d_region(xc, None, _region_w(w[c0:c0 + co]), CONV_S2, n, org, size, None, None,
+                                        list(pad)))
+                c0 += co
+            y = _cf(torch.cat(ys, -1) if len(ys) > 1 else ys[0])
+        else:
+            y = tap_gemm.conv3d_box(x, w, 2, tuple(pad_lo), tuple(size))
         ctx.save_for_backward(x, w)
         ctx.geo = (tuple(pad_lo), tuple(size))
-        return _cf(torch.cat(ys, -1) if len(ys) > 1 else ys[0])
+        ctx.hip_bwd = hip_bwd
+        return y
 
     @staticmethod
     def backward(ctx, gy):
         x, w = ctx.saved_tensors
-        gx, gw = tap_gemm.conv3d_backward(x, w, 2, ctx.geo[0], ctx.geo[1], gy, ctx.needs_input_grad[0],
-                                          ctx.needs_input_grad[1])
-        return gx, gw, None, None, None, None
+        if not ctx.hip_bwd:
+            gx, gw = tap_gemm.conv3d_backward(x, w, 2, ctx.geo[0], ctx.geo[1], gy, ctx.needs_input_grad[0],
+                                              ctx.needs_input_grad[1])
+            return gx, gw, None, None, None, None, None, None
+        from . import ops
+        gy_cl = gy.permute(0, 2, 3, 4, 1).contiguous()
+        gx = gw = None
+        if ctx.needs_input_grad[0]:
+            gx = ops.conv3d_s2_region_dgrad(gy_cl, w, tuple(x.shape[2:]), ctx.geo[0])
+        if ctx.needs_input_grad[1]:
+            gw = ops.conv3d_s2_region_wgrad(x, gy_cl, ctx.geo[0])
+        return gx, gw, None, None, None, None, None, None
 
 
 def _region_w_adjoint(w):   # Conv3d weight [co, ci, 3, 3, 3] -> the input gradient's [27][ci][co], taps flipped
@@ -142,7 +174,11 @@ class _T2Box(torch.autograd.Function):
 
 
 def s2_box(x, w, out_reg, pad, pad_lo, splits):
-    return _S2Box.apply(x, w, out_reg, pad, pad_lo, splits)
+    """Forward and backward kind are decided here, before apply.  _conv_s2_region comes here when either
+    switch is on: the forward is the HIP kernel when MVS_TRAIN_REGION_FWD names "s2", and the tap GEMMs when
+    only MVS_TRAIN_S2_BWD brought the layer here (a direct call with neither switch keeps the HIP forward)."""
+    hip_bwd = s2_bwd_enabled(x) and x.shape[1] == 32 and tuple(splits) == S2_SPLITS
+    return _S2Box.apply(x, w, out_reg, pad, pad_lo, splits, enabled(x, "s2") or not s2_bwd_enabled(x), hip_bwd)
 
 
 def s1_valid(xin, w):

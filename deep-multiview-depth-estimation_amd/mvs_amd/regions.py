@@ -97,9 +97,10 @@ def _conv_s2_region(x, weight, out_reg, pad, splits=None):
             pl.append(ca - a)
         whole = all(s_.start == 0 and s_.stop == d for s_, d in zip(sl, n))
         from . import region_train
-        if (whole and splits is not None and region_train.enabled(x, "s2") and x.shape[1] == 32
-                and tuple(splits) in (region_train.S2_SPLITS, (16,), (32,), (64,))):
-            return region_train.s2_box(x, weight, out_reg, pad, tuple(pl), tuple(splits))   # HIP forward
+        if (whole and splits is not None and x.shape[1] == 32
+                and tuple(splits) in (region_train.S2_SPLITS, (16,), (32,), (64,))
+                and (region_train.enabled(x, "s2") or region_train.s2_bwd_enabled(x))):
+            return region_train.s2_box(x, weight, out_reg, pad, tuple(pl), tuple(splits))   # HIP forward / backward
         if not whole:   # (a whole-extent slice: no copy back in the backward)
             x = x[:, :, sl[0], sl[1], sl[2]]
         return tap_gemm.conv3d_box(x, weight, 2, tuple(pl), tuple(extent(out_reg)))

@@ -17,7 +17,7 @@
 extern "C" {
 #endif
 
-#define MVS_TRAIN_ABI_VERSION 1
+#define MVS_TRAIN_ABI_VERSION 1   /* added entry points do not bump it: only a changed one would */
 
 /* Training-extension ABI version of the loaded library (MVS_TRAIN_ABI_VERSION at build time). */
 int mvs_train_abi_version(void);
@@ -37,6 +37,32 @@ int mvs_train_abi_version(void);
 size_t mvs_conv3d_region_wgrad_workspace_bytes(int batch, int channels, const int* in_size);
 int mvs_conv3d_region_wgrad(const float* x, const float* gy, int batch, int channels, const int* in_size,
                             float* dw, float* workspace, void* stream);
+
+/* Backward of the stacked stride-2 region convolution nn.Conv3d(32, 112, 3, stride=2, bias=False) of the whole
+ * cost volume on an output box (model.py:101-107 conv_1_0 / conv_2_0 / conv_3_0 stacked 16 + 32 + 64 through
+ * _conv_s2_region): output voxel o reads inputs 2 * o - pad_lo + t per dim, t = 0..2, inputs off the volume
+ * are 0.  The channel counts are FIXED: 32 in, 112 out.
+ *   x   [batch][32][D][H][W]            the volume, NCDHW, read in place; dims = {D, H, W} (HOST int[3])
+ *   gy  [batch][Oz][Oy][Ox][112]        channels-last output gradient; out_size = {Oz, Oy, Ox} (HOST int[3])
+ *   dw  [112][32][3][3][3]              nn.Conv3d's weight layout
+ *   w27 [27][32][112]                   the weight as [tap][ci][co]
+ *   gx  [batch][32][D][H][W]            NCDHW, every element written
+ * pad_lo (HOST int[3]): every pad_lo[k] >= 0, dims[k] >= 1, out_size[k] >= 1; every device pointer
+ * contiguous fp32 with a 16-byte-aligned base.  batch * D * H * W and batch * Oz * Oy * Ox below 2^31 and
+ * one sample of gy below 4 GB (else MVS_ERR_TOO_LARGE).
+ *   wgrad: dw[co][ci][t] = sum over b and o of gy[b][o][co] * x[b][2 o - pad_lo + t][ci]: fp32 on the
+ *          f32-input matrix cores, partial sums per workgroup reduced in a fixed order (bit-reproducible; no
+ *          atomics; the workspace need not be zeroed).  workspace:
+ *          mvs_conv3d_s2_region_wgrad_workspace_bytes(batch, dims, out_size) bytes (0 for arguments the
+ *          launch would refuse).
+ *   dgrad: gx[b][ci][i] = sum over t and co of gy[b][(i + pad_lo - t) / 2][co] * w[co][ci][t] over the t with
+ *          i + pad_lo - t even and the quotient inside the box: four partial sums per output (gy channels
+ *          0-15 | 16-47 | 48-79 | 80-111), added once as (p0 + p1) + (p2 + p3). */
+size_t mvs_conv3d_s2_region_wgrad_workspace_bytes(int batch, const int* dims, const int* out_size);
+int mvs_conv3d_s2_region_wgrad(const float* x, const float* gy, int batch, const int* dims, const int* pad_lo,
+                               const int* out_size, float* dw, float* workspace, void* stream);
+int mvs_conv3d_s2_region_dgrad(const float* gy, const float* w27, int batch, const int* dims, const int* pad_lo,
+                               const int* out_size, float* gx, void* stream);
 
 #ifdef __cplusplus
 }
