@@ -2,7 +2,8 @@
 mvs_amd/region_train.py _S1Valid: the input gradient on the forward's region kernel in its adjoint
 geometry, the weight gradient on csrc/conv3d_region_wgrad.hip) against float64 torch autograd, the weight
 gradient's tap / voxel / channel placement on exact impulses, its bit-reproducibility whatever the
-workspace held, the default (tap-GEMM) backward unchanged, and the regulariser's whole autograd chain."""
+workspace held, the default (tap-GEMM) backward unchanged, and the regulariser's whole autograd chain.
+(One pass of the weight gradient's tile loop throughout; the multi-pass cases: test_region_train_multipass.py.)"""
 import copy
 
 import pytest

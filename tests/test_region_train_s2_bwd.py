@@ -2,7 +2,8 @@
 _S2Box: the weight gradient on csrc/conv3d_s2_wgrad.hip from the NCDHW volume in place, the input gradient on
 the region kernel's transposed mode with four partial sums per output) against float64 torch autograd, both
 gradients' placement on exact impulses, the weight gradient's bit-reproducibility whatever the workspace held,
-the autograd routing with either forward, the default path unchanged, and the regulariser's whole chain."""
+the autograd routing with either forward, the default path unchanged, and the regulariser's whole chain.
+(At most two passes of the weight gradient's tile loop; the multi-pass cases: test_region_train_multipass.py.)"""
 import copy
 import functools
 
