@@ -3,7 +3,11 @@
 // Autograd of costvolume.py:14 (d cv / d x_v = 2 (x_v - mean) / V) composed with the grid_sample
 // backward of homography.py:86 (each sample's gradient is scattered to its 4 bilinear taps), as
 // train.py:103 exercises it.  No warped volume is stored: the samples are recomputed from the
-// forward's packed features (packed.h), exactly as the forward computed them.
+// forward's packed features (packed.h) with the forward's taps and fp32 weights, but summed in fp64
+// (sample64): the coefficient needs x_v - mean, and where a sample is within a fraction of a percent of
+// the mean the fp32 samples' own rounding (eps32 |x_v|) was the whole error of that contribution --
+// one element at 1.04 of the 1e-5 A bound of DESIGN.md §3.6 on a rig whose planes share one tap
+// (tests/test_camera_geometry.py, quarter_turn).  The difference is rounded to fp32 once.
 //
 // LDS accumulation never uses fp32 atomics: on gfx950 ds_add_f32 runs at 0.20 T lanes/s against
 // 4.3 T for ds_add_f64 and 5.1 T for ds_add_u64 (tools/microbench/atomic_patterns.hip).  Two modes:
@@ -174,6 +178,17 @@ __device__ Box tile_box(const float* __restrict__ G, int px0, int py0, int px1, 
   return b;
 }
 
+// One bilinear sample of 4 channels in fp64 from the fp32 taps and the fp32 weights of tap_weights()
+// (every product exact, three roundings of 2^-53): x_v to far below the fp32 coefficient's own rounding.
+__device__ inline void sample64(const f4v (&t)[4], float wx, float wy, double (&o)[4]) {
+  float wt[4];
+  tap_weights(wx, wy, wt);
+  const double w0 = (double)wt[0], w1 = (double)wt[1], w2 = (double)wt[2], w3 = (double)wt[3];
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    o[j] = fma((double)t[3][j], w3, fma((double)t[2][j], w2, fma((double)t[1][j], w1, (double)t[0][j] * w0)));
+}
+
 // ---- main kernel (2 <= V <= 8) -----------------------------------------------------------------
 // DET = false (default): the LDS footprint images accumulate in fp64 (ds_add_f64, ~4.3 T lanes/s;
 // each contribution is an exact fp32 product widened once) and are flushed to grad_feat with fp32
@@ -230,13 +245,26 @@ __global__ __launch_bounds__(kBlock) void cost_volume_bwd_kernel(
 
   const float xn = norm_coord(active ? px : 0, w), yn = norm_coord(active ? py : 0, h);
   const uint32_t pix = (uint32_t)(active ? py : 0) * (uint32_t)w + (uint32_t)(active ? px : 0);
-  const float4 r4 = refs[((size_t)b * c4 + ch) * hw + pix];
-  const f4v x0 = {r4.x, r4.y, r4.z, r4.w};
+  (void)refs;   // the forward's fp32 reference samples: resampled in fp64 below instead
   const f4v inv_v = {1.0f / (float)V, 1.0f / (float)V, 1.0f / (float)V, 1.0f / (float)V};
   const f4v two_inv_v = inv_v + inv_v;
-  const ViewDiv vd = view_div(V);   // the forward's mean (packed.h variance_law4)
+  const double inv_v64 = 1.0 / (double)V;
   const int soff = (int)((uint32_t)ch * pg.plane * 16u);
   const int row_bytes = pg.pitch * 16;
+  // the reference view's sample (plane independent: its matrix of shard plane 0, as the forward's
+  // prologue and ref_scatter_kernel use it), in fp64
+  double x0[4];
+  {
+    float G[9];
+    load_matrix_uniform(uniform_ptr(sampling + (size_t)(b * V) * Dc * 9), G);
+    uint32_t pos0;
+    float wx0, wy0;
+    src_coords(G, xn, yn, h, w, active, pos0, wx0, wy0);
+    const Rsrc r0 = make_rsrc(uniform_ptr(packed + (size_t)(b * V) * c4 * pg.plane), (uint32_t)c4 * pg.plane * 16u);
+    f4v t0[4];
+    load_taps(r0, tap_offset(pos0, pg), soff, row_bytes, t0);
+    sample64(t0, wx0, wy0, x0);
+  }
   // grad_cv of channel 4 ch + j, plane k0 + pl at this pixel: byte j * cst_bytes + (pl * hw + pix) * 4
   const int nch = min(C - ch * 4, 4);
   const uint32_t cst_bytes = (uint32_t)Dc * hw * 4u;   // < 2^29 (mvs_cost_volume_bwd checks 16 Dc hw)
@@ -391,20 +419,27 @@ __global__ __launch_bounds__(kBlock) void cost_volume_bwd_kernel(
         load_taps(prs[s], tap_offset(pos[s], pg), soff, row_bytes, tp[s]);
       }
       g_next = load_g(min(pl + 1, ke - 1));
-      f4v xs[NS];
-      f4v sum = x0;
+      // (held for every view: forming them again where they are used made the compiler hoist both
+      // passes, 256 VGPRs at V >= 5)
+      double xs[NS][4];
+      double mean[4] = {x0[0], x0[1], x0[2], x0[3]};
 #pragma unroll
       for (int s = 0; s < NS; ++s) {
-        xs[s] = bilerp(tp[s], wx[s], wy[s]);
-        sum += xs[s];
+        sample64(tp[s], wx[s], wy[s], xs[s]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) mean[j] += xs[s][j];
       }
-      const f4v nmean = -div_views4(sum, vd);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) mean[j] *= inv_v64;
       const f4v k2 = two_inv_v * g;
-      if (s0 == 0) racc += k2 * (x0 + nmean);
+      if (s0 == 0)
+        racc += k2 * f4v{(float)(x0[0] - mean[0]), (float)(x0[1] - mean[1]), (float)(x0[2] - mean[2]),
+                         (float)(x0[3] - mean[3])};
 #pragma unroll
       for (int s = 0; s < NS; ++s) {
         if (s < s0 || s >= s1) continue;   // uniform
-        const f4v cs = k2 * (xs[s] + nmean);
+        const f4v cs = k2 * f4v{(float)(xs[s][0] - mean[0]), (float)(xs[s][1] - mean[1]),
+                                (float)(xs[s][2] - mean[2]), (float)(xs[s][3] - mean[3])};
         const float ex = 1.0f - wx[s], ny = 1.0f - wy[s];
         const float wt[4] = {ny * ex, ny * wx[s], wy[s] * ex, wy[s] * wx[s]};
         const int cx = pos_x(pos[s]), cy = pos_y(pos[s]);
@@ -556,19 +591,21 @@ __global__ __launch_bounds__(kBlock) void cost_volume_bwd_generic_kernel(
   for (int v = 0; v < V; ++v) make_taps(sampling + ((size_t)(it.b * V + v) * Dc + it.kk) * 9, xn, yn, h, w, tp[v]);
   const float* fb = feat + (size_t)it.b * V * C * hw;
   const float inv_v = 1.0f / (float)V;
-  const ViewDiv vd = view_div(V);
   for (int c = 0; c < C; ++c) {
     const float g = grad_cv[(((size_t)it.b * C + c) * Dc + it.kk) * hw + p];
-    float val[MVS_MAX_VIEWS];
-    float sum = 0.0f;
+    double val[MVS_MAX_VIEWS];   // the samples in fp64 from the fp32 taps and weights (see sample64)
+    double sum = 0.0;
     for (int v = 0; v < V; ++v) {
-      val[v] = gather(fb + ((size_t)v * C + c) * hw, tp[v]);
+      const char* pb = reinterpret_cast<const char*>(fb + ((size_t)v * C + c) * hw);
+      auto ld = [&](int t) { return (double)*reinterpret_cast<const float*>(pb + tp[v].off[t]); };
+      val[v] = fma(ld(3), (double)tp[v].wt[3],
+                   fma(ld(2), (double)tp[v].wt[2], fma(ld(1), (double)tp[v].wt[1], ld(0) * (double)tp[v].wt[0])));
       sum += val[v];
     }
-    const float nmean = -div_views(sum, vd);   // the forward's mean (common.h variance_law)
+    const double mean = sum / (double)V;
     const float k2 = (inv_v + inv_v) * g;
     for (int v = 0; v < V; ++v) {
-      const float coef = k2 * (val[v] + nmean);
+      const float coef = k2 * (float)(val[v] - mean);
       const size_t plane = ((size_t)(it.b * V + v) * C + c) * hw;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {

@@ -641,8 +641,15 @@ def _sam_backward(ctx, grad_depth):
     db = d_batch.to(p).reshape(-1, d)
     if db.shape[0] == 1 and b > 1:
         db = db.expand(b, d)
-    den = (p * mask).sum(1, keepdim=True)
-    g = mask * (db.view(b, d, 1, 1) - depth) / den * grad_depth
+    # (d_r - depth) / den as (d_r den - num) / den^2 from this pass's own num and den, not from the stored
+    # fp32 depth: with one kept plane (n_est = 1) depth = d_r P_r / P_r can be an ulp off d_r, and
+    # dividing that ulp by a small P_r gave gradients of order 10 where the derivative is exactly 0;
+    # d_r P_r - P_r d_r is 0 in any arithmetic
+    dbv = db.view(b, d, 1, 1)
+    pm = p * mask
+    den = pm.sum(1, keepdim=True)
+    num = (pm * dbv).sum(1, keepdim=True)
+    g = mask * (dbv * den - num) / (den * den) * grad_depth
     return g.unsqueeze(1), None, None
 
 

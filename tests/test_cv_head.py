@@ -29,15 +29,7 @@ import torch
 DEV = torch.device("cuda", 0)
 
 
-def _regions(n, pad):
-    from mvs_amd import model as M
-    full = tuple((0, d - 1) for d in n)
-    B = M._tconv_input_region(full, n, pad)
-    C2 = M._tconv_input_region(B, n, pad)
-    h1, h2 = M._grow(B, n, 1), M._grow(C2, n, 1)
-    lo = [max(2 * a - p, 0) for (a, _), p in zip(h2, pad)]
-    hi = [min(2 * b - p + 2, d - 1) + 1 for (_, b), p, d in zip(h2, pad, n)]
-    return h1, lo, hi
+from synthetic_cameras import regions as _regions   # shared with tests/test_camera_geometry.py
 
 
 def test_bare_split_volume_is_rejected():
