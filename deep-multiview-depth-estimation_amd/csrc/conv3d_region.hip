@@ -57,6 +57,7 @@ __device__ inline void store_out(float* __restrict__ y, const Geo& g, int b, int
 }
 
 // QM (S2 only): input layout of the volume -- 0 NCDHW, 1 fp32 channel quads, 2 bf16 channel quads --
+// 4 channels-last x[b][z][y][x][c] (the transposed layers' input gradient: gy as the volume) --
 // a template parameter, so the K loop has no per-load layout branches and (S1 / S2: no parity
 // classes) unrolls into one basic block the scheduler can software-pipeline (loads of later taps
 // issued under the MFMAs of earlier ones)
@@ -66,7 +67,9 @@ __device__ inline void store_out(float* __restrict__ y, const Geo& g, int b, int
 // PS: independent partial sums per output.  1: one accumulation chain over every (tap, channel) -- every
 // forward instantiation.  4 (CI = 112, the stacked stride-2 layers' input gradient): one chain per channel
 // group (16 | 32 | 32 | 32: conv_1_0, conv_2_0 and the halves of conv_3_0), added once in the epilogue as
-// (p0 + p1) + (p2 + p3) -- a chain is at most 8 taps x 32 channels long instead of 8 x 112.
+// (p0 + p1) + (p2 + p3) -- a chain is at most 8 taps x 32 channels long instead of 8 x 112.  3 (S2 from the
+// channels-last volume, the transposed layers' input gradient): one chain per tap plane tz, added once as
+// (p0 + p1) + p2 -- a chain is 9 taps x CI channels long instead of 27 x CI.
 template <int MODE, int CI, int CO, int RB, int QM, int CLS, int PS = 1>
 __device__ __forceinline__ void region_conv(
     const float* __restrict__ x, const float* __restrict__ x2, const float* __restrict__ w,
@@ -75,7 +78,10 @@ __device__ __forceinline__ void region_conv(
   constexpr int NB = CO / 16;          // column blocks
   static_assert(CI % 16 == 0 && CO % 16 == 0, "channel counts in multiples of 16");
   static_assert((MODE == kT2) == (CLS >= 0), "parity classes: transposed convolutions");
-  static_assert(PS == 1 || (PS == 4 && CI == 112), "partial sums: the 112-channel input gradient only");
+  static_assert(PS == 1 || (PS == 4 && CI == 112) || (PS == 3 && MODE == kS2 && QM == 4),
+                "partial sums: the input gradients only");
+  static_assert(QM != 4 || MODE == kS2, "channels-last volume: the stride-2 mode");
+  constexpr bool kPlanes = MODE == kS2 && QM != 4;   // the input is read per channel plane / quad plane
   const int lane = (int)threadIdx.x & 63;
   const int m = lane & 15, kq = lane >> 4;   // MFMA row / K index of this lane's A value
   const int b = (int)blockIdx.z;
@@ -180,9 +186,9 @@ __device__ __forceinline__ void region_conv(
 #pragma unroll
       for (int cb = 0; cb < CI / 16; ++cb) {
         const int c4 = cb * 16 + kq * 4;
-        const int ps = PS == 1 ? 0 : (cb + 1) / 2;   // this channel block's partial sum
+        const int ps = PS == 1 ? 0 : PS == 3 ? tz : (cb + 1) / 2;   // this (tap plane's /) channel block's partial sum
         Rsrc rs, rs2;
-        if constexpr (MODE == kS2) {
+        if constexpr (kPlanes) {
           if constexpr (QM == 2)   // bf16 quads: 8 bytes per voxel and quad
             rs = make_rsrc(reinterpret_cast<const char*>(x) + ((size_t)b * (CI / 4) + cb * 4) * rvol * 8,
                            (uint32_t)(rvol * 32));
@@ -202,7 +208,7 @@ __device__ __forceinline__ void region_conv(
           for (int rb = 0; rb < RB; ++rb) {
             const uint32_t vx = vox[tx][rb];
             f4v v;
-            if constexpr (MODE == kS2) {
+            if constexpr (kPlanes) {
               if constexpr (QM == 2) {   // the bf16 quad: one 8-byte load, widened (exact)
                 typedef __attribute__((ext_vector_type(2))) unsigned v2u;
                 const v2u p = __builtin_amdgcn_raw_buffer_load_b64(
@@ -269,6 +275,7 @@ __device__ __forceinline__ void region_conv(
         float v = acc[0][rb][nb][r];
         if constexpr (PS == 4)
           v = (v + acc[1][rb][nb][r]) + (acc[PS - 2][rb][nb][r] + acc[PS - 1][rb][nb][r]);
+        if constexpr (PS == 3) v = (v + acc[1][rb][nb][r]) + acc[PS - 1][rb][nb][r];
         if (bn_scale) v = fmaxf((v - mu) * sc + sh, 0.0f);
         vmax = fmaxf(vmax, fabsf(v));
         store_out(y, g, b, co, vz, vy, vx, CO, v);
@@ -573,6 +580,35 @@ void launch_conv3d_s2_dgrad(const float* gy, const float* w27, float* gx, int B,
     g.stn[d] = n[d];
   }
   launch_mode<kT2, 112, 32, 2, 0, 4>(gy, nullptr, w27, gx, nullptr, nullptr, nullptr, B, g, s);
+}
+
+// Input gradient of a transposed region convolution (deconv_3_0 64 -> 32, deconv_2_0 32 -> 16: input voxel i
+// reaches box outputs 2 i - crop + t): gx[b][i][ci] = sum over taps t and co of gy[b][2 i - crop + t][co]
+// w[ci][co][t] -- the stride-2 mode with gy (channels-last, CF = 32 or 16 channels, the box `out`) as the volume,
+// pad = crop, no tap flip, x's extent `in` as the output box, written channels-last, w27 [27][CC][CF], one partial
+// sum per tap plane.
+int launch_conv3d_t2_dgrad(const float* gy, const float* w27, float* gx, int B, int CC, int CF, const int* in,
+                           const int* crop, const int* out, hipStream_t s) {
+  Geo g;
+  g.y_bound = nullptr;
+  g.absmax = nullptr;
+  g.out_cf = 0;
+  g.in_c4 = 0;
+  for (int d = 0; d < 3; ++d) {
+    g.n[d] = out[d];
+    g.o0[d] = 0;
+    g.on[d] = in[d];
+    g.i0[d] = 0;
+    g.in[d] = out[d];
+    g.pad[d] = crop[d];
+    g.st0[d] = 0;
+    g.stn[d] = in[d];
+  }
+  if (CC == 64 && CF == 32) launch_mode<kS2, 32, 64, 2, 4, 3>(gy, nullptr, w27, gx, nullptr, nullptr, nullptr, B, g, s);
+  else if (CC == 32 && CF == 16)
+    launch_mode<kS2, 16, 32, 2, 4, 3>(gy, nullptr, w27, gx, nullptr, nullptr, nullptr, B, g, s);
+  else return MVS_ERR_INVALID_ARGUMENT;
+  return MVS_OK;
 }
 
 }  // namespace mvs

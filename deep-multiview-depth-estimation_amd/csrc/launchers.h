@@ -111,6 +111,17 @@ void launch_conv3d_s2_wgrad(const float* x, const float* gy, int B, const int* n
 // transposed mode, four partial sums per output)
 void launch_conv3d_s2_dgrad(const float* gy, const float* w27, float* gx, int B, const int* n, const int* pad_lo,
                             const int* out, hipStream_t s);
+// csrc/conv3d_t2_wgrad.hip: weight gradient of the transposed region convolutions CC -> CF = 64 -> 32 / 32 -> 16
+// (x channels-last [B][in...][CC], gy channels-last [B][out...][CF] read in place, input voxel i reaches box
+// outputs 2 i - crop + t; dw [CC][CF][27]); part: the workspace
+bool conv3d_t2_wgrad_supported(int CC, int CF);
+size_t conv3d_t2_wgrad_workspace_bytes(int B, int CC, int CF, const int* in, const int* out);
+void launch_conv3d_t2_wgrad(const float* x, const float* gy, int B, int CC, int CF, const int* in, const int* crop,
+                            const int* out, float* part, float* dw, hipStream_t s);
+// csrc/conv3d_region.hip: their input gradient gx channels-last [B][in...][CC] from gy and w27 [27][CC][CF] (the
+// stride-2 mode from a channels-last volume, one partial sum per tap plane)
+int launch_conv3d_t2_dgrad(const float* gy, const float* w27, float* gx, int B, int CC, int CF, const int* in,
+                           const int* crop, const int* out, hipStream_t s);
 void launch_conv3d_k3_narrow(const float* in, int in_c4, bool wino_z, const float* weight, float* out, int B,
                              int Cin, int Cout, int D, int H, int W, const float* bn_scale, const float* bn_shift,
                              const float* bn_mean, hipStream_t s, const float* in2 = nullptr,

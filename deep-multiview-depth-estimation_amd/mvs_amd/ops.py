@@ -841,6 +841,76 @@ def conv3d_s2_region_dgrad(gy_cl: torch.Tensor, w: torch.Tensor, dims, pad_lo) -
     return gx
 
 
+T2_BWD_CHANNELS = ((64, 32), (32, 16))   # (c_in, c_out) of mvs_conv3d_t2_region_wgrad / _dgrad: deconv_3_0, deconv_2_0
+
+
+def _cl5(t):
+    """A logical NCDHW tensor as contiguous channels-last [B, d, h, w, C] fp32: no copy when its memory already
+    is (what autograd hands the transposed layers' backward at the training shapes)."""
+    return t.to(_F32).permute(0, 2, 3, 4, 1).contiguous()
+
+
+def conv3d_t2_region_wgrad(x: torch.Tensor, gy: torch.Tensor, crop) -> torch.Tensor:
+    """Weight gradient of a transposed region convolution nn.ConvTranspose3d(c_in, c_out, 3, stride=2, bias=False)
+    on an output box (model.py:117-120 deconv_3_0 / deconv_2_0: input voxel i reaches box output 2 i - crop + t,
+    taps outside the box dropped) from its input x [B, c_in, Iz, Iy, Ix] and output gradient gy
+    [B, c_out, Oz, Oy, Ox], both logical NCDHW and read as channels-last memory (in place when they are; copied
+    otherwise): dw [c_in, c_out, 3, 3, 3] on the f32 matrix cores (mvs_conv3d_t2_region_wgrad of the training
+    extension, deterministic).  (c_in, c_out) in T2_BWD_CHANNELS."""
+    _require_gpu(x, "x")
+    _require_gpu(gy, "gy")
+    lib = _lib.load()
+    if (x.dim() != 5 or gy.dim() != 5 or x.shape[0] != gy.shape[0]
+            or (x.shape[1], gy.shape[1]) not in T2_BWD_CHANNELS):
+        raise ValueError("x [B, c_in, Iz, Iy, Ix] and gy [B, c_out, Oz, Oy, Ox] with (c_in, c_out) in %s expected, "
+                         "got %s and %s" % (T2_BWD_CHANNELS, tuple(x.shape), tuple(gy.shape)))
+    cr = _ints3(_pad3(crop))
+    b, cin, cout = x.shape[0], x.shape[1], gy.shape[1]
+    x_cl = _cl5(x)
+    gy_cl = _cl5(gy.to(x.device))
+    size, out = _ints3(x_cl.shape[1:4]), _ints3(gy_cl.shape[1:4])
+    nbytes = lib.mvs_conv3d_t2_region_wgrad_workspace_bytes(b, cin, cout, size, out)
+    if nbytes == 0:
+        raise ValueError("input %s, box %s: every extent >= 1, B * voxels < 2^31 and a sample of gy < 4 GB expected"
+                         % (tuple(x_cl.shape[1:4]), tuple(gy_cl.shape[1:4])))
+    ws = torch.empty(nbytes // 4, device=x.device, dtype=_F32)
+    dw = torch.empty((cin, cout, 3, 3, 3), device=x.device, dtype=_F32)
+    st = lib.mvs_conv3d_t2_region_wgrad(_lib.ptr(x_cl), _lib.ptr(gy_cl), b, cin, cout, size, cr, out, _lib.ptr(dw),
+                                        _lib.ptr(ws), _lib.stream_handle(x.device))
+    _lib.check(st, "mvs_conv3d_t2_region_wgrad")
+    return dw
+
+
+def conv3d_t2_region_dgrad(gy: torch.Tensor, w: torch.Tensor, in_size, crop) -> torch.Tensor:
+    """Input gradient of the same convolution from gy [B, c_out, Oz, Oy, Ox] (logical NCDHW, read as channels-last
+    memory) and its weight w [c_in, c_out, 3, 3, 3]: gx [B, c_in, *in_size], logical NCDHW over channels-last
+    memory (every element written), gx[b, :, i] = sum over taps t and co of gy[b, co, 2 i - crop + t] w[:, co, t]
+    (mvs_conv3d_t2_region_dgrad: the stride-2 mode of the fp32 region kernel, one partial sum per tap plane)."""
+    _require_gpu(gy, "gy")
+    _require_gpu(w, "w")
+    lib = _lib.load()
+    in_size = tuple(int(d) for d in in_size)
+    if (gy.dim() != 5 or w.dim() != 5 or (w.shape[0], w.shape[1]) not in T2_BWD_CHANNELS
+            or gy.shape[1] != w.shape[1] or tuple(w.shape[2:]) != (3, 3, 3)):
+        raise ValueError("gy [B, c_out, Oz, Oy, Ox] and w [c_in, c_out, 3, 3, 3] with (c_in, c_out) in %s expected, "
+                         "got %s and %s" % (T2_BWD_CHANNELS, tuple(gy.shape), tuple(w.shape)))
+    if len(in_size) != 3 or min(in_size) < 1:
+        raise ValueError("in_size: three ints >= 1 expected, got %s" % (in_size,))
+    cr = _ints3(_pad3(crop))
+    b, cin, cout = gy.shape[0], w.shape[0], w.shape[1]
+    gy_cl = _cl5(gy)
+    w27 = w.detach().to(device=gy.device, dtype=_F32).permute(2, 3, 4, 0, 1).reshape(27, cin, cout).contiguous()
+    size, out = _ints3(in_size), _ints3(gy_cl.shape[1:4])
+    if lib.mvs_conv3d_t2_region_wgrad_workspace_bytes(b, cin, cout, size, out) == 0:   # (one geometry check for both)
+        raise ValueError("input %s, box %s: every extent >= 1, B * voxels < 2^31 and a sample of gy < 4 GB expected"
+                         % (in_size, tuple(gy_cl.shape[1:4])))
+    gx = torch.empty((b,) + in_size + (cin,), device=gy.device, dtype=_F32)
+    st = lib.mvs_conv3d_t2_region_dgrad(_lib.ptr(gy_cl), _lib.ptr(w27), b, cin, cout, size, cr, out, _lib.ptr(gx),
+                                        _lib.stream_handle(gy.device))
+    _lib.check(st, "mvs_conv3d_t2_region_dgrad")
+    return gx.permute(0, 4, 1, 2, 3)
+
+
 @torch.library.custom_op("mvs::conv_head_fp32", mutates_args=())
 def conv_head_fp32(cv4: torch.Tensor, w0: torch.Tensor, bn0_scale: Optional[torch.Tensor],
                    bn0_shift: Optional[torch.Tensor], bn0_mean: Optional[torch.Tensor], w1: torch.Tensor,

@@ -13,7 +13,9 @@ the stride-1 layers' backward onto HIP kernels as well: the input gradient on th
 in its adjoint geometry, the weight gradient on csrc/conv3d_region_wgrad.hip.  MVS_TRAIN_S2_BWD
 (s2_bwd_enabled(), default "taps") does the same for the stacked stride-2 layer: the input gradient on the
 region kernel's transposed mode, the weight gradient on csrc/conv3d_s2_wgrad.hip, both from the NCDHW volume
-in place."""
+in place.  MVS_TRAIN_T2_BWD (t2_bwd_enabled(), default "taps") does it for deconv_3_0 / deconv_2_0: the input
+gradient on the region kernel's stride-2 mode with the channels-last output gradient as the volume, the weight
+gradient on csrc/conv3d_t2_wgrad.hip; deconv_1_0 stays on the tap GEMMs."""
 import os
 
 import torch
@@ -154,23 +156,45 @@ class _S1Valid(torch.autograd.Function):
         return gx, gw
 
 
+def t2_bwd_enabled(x):
+    """The backward of the transposed region convolutions deconv_3_0 / deconv_2_0 (T2_SHAPES) runs on the HIP
+    kernels (ops.conv3d_t2_region_wgrad / conv3d_t2_region_dgrad).  MVS_TRAIN_T2_BWD, read on every call: "hip",
+    or "taps" (the per-tap GEMMs; the default).  A switch of its own: MVS_TRAIN_REGION_BWD never names "t2"."""
+    on = os.environ.get("MVS_TRAIN_T2_BWD", "taps") == "hip"
+    return on and x.is_cuda and x.dtype == torch.float32
+
+
 class _T2Box(torch.autograd.Function):
+    """The transposed convolution on its output box, forward on the region kernel.  hip_bwd (decided by the
+    caller, t2_box: T2_SHAPES under MVS_TRAIN_T2_BWD=hip): the backward on ops.conv3d_t2_region_wgrad /
+    conv3d_t2_region_dgrad, reading gy in the channels-last memory autograd delivers it in and returning gx
+    channels-last like x; else tap_gemm.conv_transpose3d_backward.  Only x and w are saved."""
+
     @staticmethod
-    def forward(ctx, x, w, x_reg, out_reg, pad, dims, crop):
+    def forward(ctx, x, w, x_reg, out_reg, pad, dims, crop, hip_bwd=False):
         from .ops import CONV_T2, conv3d_region
         size = extent(out_reg)
         y = conv3d_region(x.permute(0, 2, 3, 4, 1).contiguous(), None, _region_wt(w), CONV_T2, list(dims),
                           origin(out_reg), size, origin(x_reg), extent(x_reg), list(pad))
         ctx.save_for_backward(x, w)
         ctx.geo = (tuple(crop), tuple(size))
+        ctx.hip_bwd = hip_bwd
         return _cf(y)
 
     @staticmethod
     def backward(ctx, gy):
         x, w = ctx.saved_tensors
-        gx, gw = tap_gemm.conv_transpose3d_backward(x, w, 2, ctx.geo[0], ctx.geo[1], gy, ctx.needs_input_grad[0],
-                                                    ctx.needs_input_grad[1])
-        return gx, gw, None, None, None, None, None
+        if not ctx.hip_bwd:
+            gx, gw = tap_gemm.conv_transpose3d_backward(x, w, 2, ctx.geo[0], ctx.geo[1], gy, ctx.needs_input_grad[0],
+                                                        ctx.needs_input_grad[1])
+            return gx, gw, None, None, None, None, None, None
+        from . import ops
+        gx = gw = None
+        if ctx.needs_input_grad[0]:
+            gx = ops.conv3d_t2_region_dgrad(gy, w, tuple(x.shape[2:]), ctx.geo[0])
+        if ctx.needs_input_grad[1]:
+            gw = ops.conv3d_t2_region_wgrad(x, gy, ctx.geo[0])
+        return gx, gw, None, None, None, None, None, None
 
 
 def s2_box(x, w, out_reg, pad, pad_lo, splits):
@@ -186,4 +210,7 @@ def s1_valid(xin, w):
 
 
 def t2_box(x, w, x_reg, out_reg, pad, dims, crop):
-    return _T2Box.apply(x, w, x_reg, out_reg, pad, dims, crop)
+    """The backward kind is decided here, before apply (deconv_1_0, 16 -> 8 with dims=None, never comes here:
+    it stays on the tap GEMMs)."""
+    hip_bwd = t2_bwd_enabled(x) and (w.shape[0], w.shape[1]) in T2_SHAPES
+    return _T2Box.apply(x, w, x_reg, out_reg, pad, dims, crop, hip_bwd)

@@ -64,6 +64,33 @@ int mvs_conv3d_s2_region_wgrad(const float* x, const float* gy, int batch, const
 int mvs_conv3d_s2_region_dgrad(const float* gy, const float* w27, int batch, const int* dims, const int* pad_lo,
                                const int* out_size, float* gx, void* stream);
 
+/* Backward of a transposed region convolution nn.ConvTranspose3d(c_in, c_out, 3, stride=2, bias=False) on an
+ * output box (model.py:117-120 deconv_3_0 / deconv_2_0 through _tconv_region): the box holds outputs
+ * [crop, crop + out_size) of the unpadded transposed convolution, input voxel i reaches box output
+ * 2 * i - crop + t per dim, t = 0..2; taps that land outside the box are dropped.  (c_in, c_out) is (64, 32)
+ * or (32, 16): anything else is MVS_ERR_INVALID_ARGUMENT.
+ *   x   [batch][Iz][Iy][Ix][c_in]       channels-last input; in_size = {Iz, Iy, Ix} (HOST int[3])
+ *   gy  [batch][Oz][Oy][Ox][c_out]      channels-last output gradient, read in place; out_size (HOST int[3])
+ *   dw  [c_in][c_out][3][3][3]          nn.ConvTranspose3d's weight layout
+ *   w27 [27][c_in][c_out]               the weight as [tap][ci][co]
+ *   gx  [batch][Iz][Iy][Ix][c_in]       channels-last, every element written
+ * crop (HOST int[3]): every crop[k] >= 0, in_size[k] >= 1, out_size[k] >= 1; every device pointer contiguous
+ * fp32 with a 16-byte-aligned base.  batch * Iz * Iy * Ix and batch * Oz * Oy * Ox below 2^31 and one sample of
+ * gy below 4 GB (else MVS_ERR_TOO_LARGE).
+ *   wgrad: dw[ci][co][t] = sum over b and i of x[b][i][ci] * gy[b][2 i - crop + t][co]: fp32 on the f32-input
+ *          matrix cores, partial sums per workgroup reduced in a fixed order (bit-reproducible; no atomics; the
+ *          workspace need not be zeroed).  workspace:
+ *          mvs_conv3d_t2_region_wgrad_workspace_bytes(batch, c_in, c_out, in_size, out_size) bytes (0 for
+ *          arguments the launch would refuse).
+ *   dgrad: gx[b][i][ci] = sum over t and co of gy[b][2 i - crop + t][co] * w[ci][co][t]: three partial sums per
+ *          output, one per tap plane tz, added once as (p0 + p1) + p2. */
+size_t mvs_conv3d_t2_region_wgrad_workspace_bytes(int batch, int c_in, int c_out, const int* in_size,
+                                                  const int* out_size);
+int mvs_conv3d_t2_region_wgrad(const float* x, const float* gy, int batch, int c_in, int c_out, const int* in_size,
+                               const int* crop, const int* out_size, float* dw, float* workspace, void* stream);
+int mvs_conv3d_t2_region_dgrad(const float* gy, const float* w27, int batch, int c_in, int c_out, const int* in_size,
+                               const int* crop, const int* out_size, float* gx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
