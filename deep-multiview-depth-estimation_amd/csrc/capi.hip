@@ -757,6 +757,58 @@ int mvs_conv3d_t2_region_dgrad(const float* gy, const float* w27, int batch, int
   return ls != MVS_OK ? ls : lc.status();
 }
 
+namespace {
+// MVS_OK when mvs_deconv3d_k3s2_wgrad / _dgrad can launch on this geometry
+int deconv3d_bwd_geometry(int batch, int c_in, int c_out, const int* in_size, const int* crop, const int* out_size) {
+  if (!in_size || !out_size || batch <= 0 || c_in != 16 || c_out != 8) return MVS_ERR_INVALID_ARGUMENT;
+  uint64_t vox = (uint64_t)batch, ovox = (uint64_t)batch, osample = 1;
+  for (int k = 0; k < 3; ++k)
+    if (in_size[k] < 1 || out_size[k] < 1 || (crop && crop[k] < 0)) return MVS_ERR_INVALID_ARGUMENT;
+  for (int k = 0; k < 3; ++k) {
+    vox *= (uint64_t)in_size[k];
+    ovox *= (uint64_t)out_size[k];
+    osample *= (uint64_t)out_size[k];
+    if (vox >= (1ull << 31) || ovox >= (1ull << 31)) return MVS_ERR_TOO_LARGE;   // 32-bit row and voxel indices
+    if (in_size[k] >= (1 << 29) || (crop && crop[k] >= (1 << 29))) return MVS_ERR_TOO_LARGE;   // 2 i - crop + t
+  }
+  if (osample * (uint64_t)c_out * sizeof(float) >= 0xFFFFFFC0ull) return MVS_ERR_TOO_LARGE;   // one sample of gy
+  return MVS_OK;
+}
+}  // namespace
+
+size_t mvs_deconv3d_k3s2_wgrad_workspace_bytes(int batch, int c_in, int c_out, const int* in_size,
+                                               const int* out_size) {
+  if (deconv3d_bwd_geometry(batch, c_in, c_out, in_size, nullptr, out_size) != MVS_OK) return 0;
+  return mvs::deconv3d_wgrad_workspace_bytes(batch, in_size, out_size);
+}
+
+int mvs_deconv3d_k3s2_wgrad(const float* x, int flags, const float* gy, int batch, int c_in, int c_out,
+                            const int* in_size, const int* crop, const int* out_size, float* dw, float* workspace,
+                            void* stream) {
+  if (!x || !gy || !dw || !workspace || !crop) return MVS_ERR_INVALID_ARGUMENT;
+  if (((uintptr_t)x | (uintptr_t)gy | (uintptr_t)dw | (uintptr_t)workspace) & 15u) return MVS_ERR_INVALID_ARGUMENT;
+  if (flags & ~MVS_LAYOUT_CHANNELS_LAST) return MVS_ERR_INVALID_ARGUMENT;
+  const int st = deconv3d_bwd_geometry(batch, c_in, c_out, in_size, crop, out_size);
+  if (st != MVS_OK) return st;
+  const mvs::LaunchCheck lc;
+  mvs::launch_deconv3d_wgrad(x, (flags & MVS_LAYOUT_CHANNELS_LAST) != 0, gy, batch, in_size, crop, out_size, workspace,
+                             dw, (hipStream_t)stream);
+  return lc.status();
+}
+
+int mvs_deconv3d_k3s2_dgrad(const float* gy, const float* w27, int flags, int batch, int c_in, int c_out,
+                            const int* in_size, const int* crop, const int* out_size, float* gx, void* stream) {
+  if (!gy || !w27 || !gx || !crop) return MVS_ERR_INVALID_ARGUMENT;
+  if (((uintptr_t)gy | (uintptr_t)w27 | (uintptr_t)gx) & 15u) return MVS_ERR_INVALID_ARGUMENT;
+  if (flags & ~MVS_LAYOUT_CHANNELS_LAST) return MVS_ERR_INVALID_ARGUMENT;
+  const int st = deconv3d_bwd_geometry(batch, c_in, c_out, in_size, crop, out_size);
+  if (st != MVS_OK) return st;
+  const mvs::LaunchCheck lc;
+  mvs::launch_deconv3d_dgrad(gy, w27, gx, (flags & MVS_LAYOUT_CHANNELS_LAST) != 0, batch, in_size, crop, out_size,
+                             (hipStream_t)stream);
+  return lc.status();
+}
+
 int mvs_conv_head_fp32_fwd(const float* cv4, int batch, int d, int h, int w, const float* w0_wz,
                            const float* bn0_scale, const float* bn0_shift, const float* bn0_mean, const float* w1,
                            const float* w1_pass, const float* bn1_scale, const float* bn1_shift,

@@ -122,6 +122,14 @@ void launch_conv3d_t2_wgrad(const float* x, const float* gy, int B, int CC, int 
 // stride-2 mode from a channels-last volume, one partial sum per tap plane)
 int launch_conv3d_t2_dgrad(const float* gy, const float* w27, float* gx, int B, int CC, int CF, const int* in,
                            const int* crop, const int* out, hipStream_t s);
+// csrc/deconv3d_region_bwd.hip: backward of deconv_1_0 (16 -> 8) on its output box (gy NCDHW [B][8][out...] read in
+// place; x and gx NCDHW [B][16][in...] or, x_cl, channels-last [B][in...][16]; input voxel i reaches box outputs
+// 2 i - crop + t; dw [16][8][27]; w27 [27][16][8]); part: the weight gradient's workspace
+size_t deconv3d_wgrad_workspace_bytes(int B, const int* in, const int* out);
+void launch_deconv3d_wgrad(const float* x, bool x_cl, const float* gy, int B, const int* in, const int* crop,
+                           const int* out, float* part, float* dw, hipStream_t s);
+void launch_deconv3d_dgrad(const float* gy, const float* w27, float* gx, bool x_cl, int B, const int* in,
+                           const int* crop, const int* out, hipStream_t s);
 void launch_conv3d_k3_narrow(const float* in, int in_c4, bool wino_z, const float* weight, float* out, int B,
                              int Cin, int Cout, int D, int H, int W, const float* bn_scale, const float* bn_shift,
                              const float* bn_mean, hipStream_t s, const float* in2 = nullptr,

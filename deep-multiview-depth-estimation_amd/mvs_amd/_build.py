@@ -18,7 +18,7 @@ SOURCES = [os.path.join(CSRC, f) for f in ("capi.hip", "plane_sampling.hip", "co
                                            "conv3d_region_split.hip", "conv2d_split.hip",
                                            "conv3d_wgrad.hip", "conv3d_s2_lds.hip",
                                            "conv3d_region_wgrad.hip", "conv3d_s2_wgrad.hip",
-                                           "conv3d_t2_wgrad.hip")]
+                                           "conv3d_t2_wgrad.hip", "deconv3d_region_bwd.hip")]
 HEADERS = [os.path.join(REPO_ROOT, "include", "mvs_cost_volume.h"),
            os.path.join(REPO_ROOT, "include", "train", "mvs_region_train.h"),
            os.path.join(CSRC, "common.h"), os.path.join(CSRC, "launchers.h"),

@@ -118,6 +118,9 @@ TRAIN_SIGNATURES = {
     "mvs_conv3d_t2_region_wgrad_workspace_bytes": (ctypes.c_size_t, [_c_int, _c_int, _c_int, _p, _p]),
     "mvs_conv3d_t2_region_wgrad": (_c_int, [_p, _p, _c_int, _c_int, _c_int, _p, _p, _p, _p, _p, _p]),
     "mvs_conv3d_t2_region_dgrad": (_c_int, [_p, _p, _c_int, _c_int, _c_int, _p, _p, _p, _p, _p]),
+    "mvs_deconv3d_k3s2_wgrad_workspace_bytes": (ctypes.c_size_t, [_c_int, _c_int, _c_int, _p, _p]),
+    "mvs_deconv3d_k3s2_wgrad": (_c_int, [_p, _c_int, _p, _c_int, _c_int, _c_int, _p, _p, _p, _p, _p, _p]),
+    "mvs_deconv3d_k3s2_dgrad": (_c_int, [_p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p, _p]),
 }
 
 

@@ -911,6 +911,86 @@ def conv3d_t2_region_dgrad(gy: torch.Tensor, w: torch.Tensor, in_size, crop) -> 
     return gx.permute(0, 4, 1, 2, 3)
 
 
+DECONV1_CHANNELS = (16, 8)   # (c_in, c_out) of mvs_deconv3d_k3s2_wgrad / _dgrad: deconv_1_0
+
+
+def _is_cl5(t):
+    """A logical NCDHW tensor whose memory is contiguous channels-last [B, d, h, w, C] (and not NCDHW as well)."""
+    return not t.is_contiguous() and t.permute(0, 2, 3, 4, 1).is_contiguous()
+
+
+def _x_layout(x):
+    """(memory, flags) of a logical NCDHW x for the deconv_1_0 backward: channels-last memory in place, anything
+    else as contiguous NCDHW."""
+    x = x.to(_F32)
+    if _is_cl5(x):
+        return x, _lib.MVS_LAYOUT_CHANNELS_LAST
+    return x.contiguous(), 0
+
+
+def deconv3d_k3s2_wgrad(x: torch.Tensor, gy: torch.Tensor, crop) -> torch.Tensor:
+    """Weight gradient of the transposed region convolution nn.ConvTranspose3d(16, 8, 3, stride=2, bias=False) on
+    an output box (model.py:121 deconv_1_0: input voxel i reaches box output 2 i - crop + t, taps outside the box
+    dropped; the forward is deconv3d_k3s2 in raw mode) from its input x [B, 16, Iz, Iy, Ix] (logical NCDHW; NCDHW or
+    channels-last memory read in place) and output gradient gy [B, 8, Oz, Oy, Ox] (NCDHW, read in place; any other
+    layout is made contiguous once): dw [16, 8, 3, 3, 3] on the f32 matrix cores (mvs_deconv3d_k3s2_wgrad of the
+    training extension, deterministic)."""
+    _require_gpu(x, "x")
+    _require_gpu(gy, "gy")
+    lib = _lib.load()
+    cin, cout = DECONV1_CHANNELS
+    if (x.dim() != 5 or gy.dim() != 5 or x.shape[0] != gy.shape[0] or x.shape[1] != cin or gy.shape[1] != cout):
+        raise ValueError("x [B, %d, Iz, Iy, Ix] and gy [B, %d, Oz, Oy, Ox] expected, got %s and %s"
+                         % (cin, cout, tuple(x.shape), tuple(gy.shape)))
+    cr = _ints3(_pad3(crop))
+    b = x.shape[0]
+    xm, flags = _x_layout(x)
+    gy = gy.to(device=x.device, dtype=_F32).contiguous()
+    size, out = _ints3(x.shape[2:]), _ints3(gy.shape[2:])
+    nbytes = lib.mvs_deconv3d_k3s2_wgrad_workspace_bytes(b, cin, cout, size, out)
+    if nbytes == 0:
+        raise ValueError("input %s, box %s: every extent >= 1, B * voxels < 2^31 and a sample of gy < 4 GB expected"
+                         % (tuple(x.shape[2:]), tuple(gy.shape[2:])))
+    ws = torch.empty(nbytes // 4, device=x.device, dtype=_F32)
+    dw = torch.empty((cin, cout, 3, 3, 3), device=x.device, dtype=_F32)
+    st = lib.mvs_deconv3d_k3s2_wgrad(_lib.ptr(xm), flags, _lib.ptr(gy), b, cin, cout, size, cr, out, _lib.ptr(dw),
+                                     _lib.ptr(ws), _lib.stream_handle(x.device))
+    _lib.check(st, "mvs_deconv3d_k3s2_wgrad")
+    return dw
+
+
+def deconv3d_k3s2_dgrad(gy: torch.Tensor, w: torch.Tensor, in_size, crop, channels_last: bool = False) -> torch.Tensor:
+    """Input gradient of the same convolution from gy [B, 8, Oz, Oy, Ox] (NCDHW, read in place; any other layout is
+    made contiguous once) and its weight w [16, 8, 3, 3, 3]: gx [B, 16, *in_size] (every element written), NCDHW
+    or, channels_last, logical NCDHW over channels-last memory (x's layout, so that what consumes it needs no
+    conversion); gx[b, :, i] = sum over taps t and co of gy[b, co, 2 i - crop + t] w[:, co, t]
+    (mvs_deconv3d_k3s2_dgrad: a gather, one partial sum per tap plane)."""
+    _require_gpu(gy, "gy")
+    _require_gpu(w, "w")
+    lib = _lib.load()
+    cin, cout = DECONV1_CHANNELS
+    in_size = tuple(int(d) for d in in_size)
+    if gy.dim() != 5 or gy.shape[1] != cout or tuple(w.shape) != (cin, cout, 3, 3, 3):
+        raise ValueError("gy [B, %d, Oz, Oy, Ox] and w [%d, %d, 3, 3, 3] expected, got %s and %s"
+                         % (cout, cin, cout, tuple(gy.shape), tuple(w.shape)))
+    if len(in_size) != 3 or min(in_size) < 1:
+        raise ValueError("in_size: three ints >= 1 expected, got %s" % (in_size,))
+    cr = _ints3(_pad3(crop))
+    b = gy.shape[0]
+    gy = gy.to(_F32).contiguous()
+    w27 = w.detach().to(device=gy.device, dtype=_F32).permute(2, 3, 4, 0, 1).reshape(27, cin, cout).contiguous()
+    size, out = _ints3(in_size), _ints3(gy.shape[2:])
+    if lib.mvs_deconv3d_k3s2_wgrad_workspace_bytes(b, cin, cout, size, out) == 0:   # (one geometry check for both)
+        raise ValueError("input %s, box %s: every extent >= 1, B * voxels < 2^31 and a sample of gy < 4 GB expected"
+                         % (in_size, tuple(gy.shape[2:])))
+    flags = _lib.MVS_LAYOUT_CHANNELS_LAST if channels_last else 0
+    gx = torch.empty((b,) + in_size + (cin,) if channels_last else (b, cin) + in_size, device=gy.device, dtype=_F32)
+    st = lib.mvs_deconv3d_k3s2_dgrad(_lib.ptr(gy), _lib.ptr(w27), flags, b, cin, cout, size, cr, out, _lib.ptr(gx),
+                                     _lib.stream_handle(gy.device))
+    _lib.check(st, "mvs_deconv3d_k3s2_dgrad")
+    return gx.permute(0, 4, 1, 2, 3) if channels_last else gx
+
+
 @torch.library.custom_op("mvs::conv_head_fp32", mutates_args=())
 def conv_head_fp32(cv4: torch.Tensor, w0: torch.Tensor, bn0_scale: Optional[torch.Tensor],
                    bn0_shift: Optional[torch.Tensor], bn0_mean: Optional[torch.Tensor], w1: torch.Tensor,

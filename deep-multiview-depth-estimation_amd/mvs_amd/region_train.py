@@ -15,7 +15,11 @@ in its adjoint geometry, the weight gradient on csrc/conv3d_region_wgrad.hip.  M
 region kernel's transposed mode, the weight gradient on csrc/conv3d_s2_wgrad.hip, both from the NCDHW volume
 in place.  MVS_TRAIN_T2_BWD (t2_bwd_enabled(), default "taps") does it for deconv_3_0 / deconv_2_0: the input
 gradient on the region kernel's stride-2 mode with the channels-last output gradient as the volume, the weight
-gradient on csrc/conv3d_t2_wgrad.hip; deconv_1_0 stays on the tap GEMMs."""
+gradient on csrc/conv3d_t2_wgrad.hip.  deconv_1_0 (16 -> 8, the full-size output, dims=None in _tconv_region)
+comes under none of these: MVS_TRAIN_DECONV1 (d1_enabled(), default "taps") moves it onto HIP kernels in both
+directions at once -- the forward on csrc/deconv3d_region.hip in raw mode (one pass instead of 27 tap passes over
+the output), the input and weight gradients on csrc/deconv3d_region_bwd.hip, reading the NCDHW output gradient in
+place and x in the channels-last memory it arrives in."""
 import os
 
 import torch
@@ -197,6 +201,57 @@ class _T2Box(torch.autograd.Function):
         return gx, gw, None, None, None, None, None, None
 
 
+D1_SHAPE = (16, 8)   # (c_in, c_out) of deconv_1_0
+
+
+def d1_enabled(x):
+    """deconv_1_0 (D1_SHAPE, the transposed layer whose output is the full-size volume) runs forward and backward
+    on the HIP kernels under autograd (ops.deconv3d_k3s2 / deconv3d_k3s2_wgrad / deconv3d_k3s2_dgrad).
+    MVS_TRAIN_DECONV1, read on every call: "hip", or "taps" (the per-tap GEMMs; the default, also when unset or
+    empty).  A switch of its own: no other switch enables it and it enables nothing else."""
+    on = os.environ.get("MVS_TRAIN_DECONV1", "taps") == "hip"
+    return on and x.is_cuda and x.dtype == torch.float32
+
+
+class _D1Box(torch.autograd.Function):
+    """deconv_1_0 on its output box: the forward on csrc/deconv3d_region.hip in raw mode (no BN, no residual; one
+    pass, y NCDHW), the backward on csrc/deconv3d_region_bwd.hip, reading gy NCDHW in place and returning gx in
+    x's layout (channels-last memory at the training shapes).  The kernel's geometry is origin and padding with
+    pad - 2 * origin = crop per dim: origin 0 and pad = crop is the same launch.  Only x and w are saved."""
+
+    @staticmethod
+    def forward(ctx, x, w, crop, size, cl):
+        from . import ops
+        y = ops.deconv3d_k3s2(x.permute(0, 2, 3, 4, 1) if cl else x, [0, 0, 0], w, list(size), list(crop),
+                              None, None, None, None, channels_last=cl)
+        ctx.save_for_backward(x, w)
+        ctx.crop, ctx.cl = tuple(crop), cl
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        from . import ops
+        x, w = ctx.saved_tensors
+        gx = gw = None
+        if ctx.needs_input_grad[0]:
+            gx = ops.deconv3d_k3s2_dgrad(gy, w, tuple(x.shape[2:]), ctx.crop, channels_last=ctx.cl)
+        if ctx.needs_input_grad[1]:
+            gw = ops.deconv3d_k3s2_wgrad(x, gy, ctx.crop)
+        return gx, gw, None, None, None
+
+
+def d1_applies(x, w):
+    """_tconv_region sends the layer to d1_box: the switch on, a GPU fp32 tensor under autograd, the (16, 8) weight."""
+    return d1_enabled(x) and torch.is_grad_enabled() and tuple(w.shape) == D1_SHAPE + (3, 3, 3)
+
+
+def d1_box(x, w, out_reg, crop):
+    """deconv_1_0 under MVS_TRAIN_DECONV1=hip (d1_applies).  Which memory layout the kernels read x in (and return
+    gx in) is decided here, before apply: channels-last in place when x's memory is, else NCDHW."""
+    from .ops import _is_cl5
+    return _D1Box.apply(x, w, tuple(crop), tuple(extent(out_reg)), _is_cl5(x))
+
+
 def s2_box(x, w, out_reg, pad, pad_lo, splits):
     """Forward and backward kind are decided here, before apply.  _conv_s2_region comes here when either
     switch is on: the forward is the HIP kernel when MVS_TRAIN_REGION_FWD names "s2", and the tap GEMMs when
@@ -211,6 +266,6 @@ def s1_valid(xin, w):
 
 def t2_box(x, w, x_reg, out_reg, pad, dims, crop):
     """The backward kind is decided here, before apply (deconv_1_0, 16 -> 8 with dims=None, never comes here:
-    it stays on the tap GEMMs)."""
+    it goes to d1_box under MVS_TRAIN_DECONV1=hip and to the tap GEMMs otherwise)."""
     hip_bwd = t2_bwd_enabled(x) and (w.shape[0], w.shape[1]) in T2_SHAPES
     return _T2Box.apply(x, w, x_reg, out_reg, pad, dims, crop, hip_bwd)

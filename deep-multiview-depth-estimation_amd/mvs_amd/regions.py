@@ -146,6 +146,8 @@ def _tconv_region(x, x_reg, weight, out_reg, pad, dims=None):
         if (dims is not None and region_train.enabled(x, "t2")
                 and (weight.shape[0], weight.shape[1]) in region_train.T2_SHAPES):
             return region_train.t2_box(x, weight, x_reg, out_reg, pad, dims, tuple(crop))   # HIP forward
+        if dims is None and region_train.d1_applies(x, weight):
+            return region_train.d1_box(x, weight, out_reg, tuple(crop))   # deconv_1_0: HIP forward and backward
         return tap_gemm.conv_transpose3d_box(x, weight, 2, tuple(crop), tuple(extent(out_reg)))
     y = F.conv_transpose3d(x, weight, stride=2)   # output q <-> volume index 2 * xlo + q - P
     sl, pads = [], []

@@ -91,6 +91,36 @@ int mvs_conv3d_t2_region_wgrad(const float* x, const float* gy, int batch, int c
 int mvs_conv3d_t2_region_dgrad(const float* gy, const float* w27, int batch, int c_in, int c_out, const int* in_size,
                                const int* crop, const int* out_size, float* gx, void* stream);
 
+/* Backward of the last transposed region convolution nn.ConvTranspose3d(16, 8, 3, stride=2, bias=False) on an
+ * output box (model.py:121 deconv_1_0 through _tconv_region; its forward is mvs_deconv3d_k3s2_fwd without BN and
+ * residual, with pad - 2 * origin = crop per dim): the box holds outputs [crop, crop + out_size) of the unpadded
+ * transposed convolution, input voxel i reaches box output 2 * i - crop + t per dim, t = 0..2; taps that land
+ * outside the box are dropped.  (c_in, c_out) must be (16, 8): anything else is MVS_ERR_INVALID_ARGUMENT.
+ *   x   [batch][16][Iz][Iy][Ix]         the input, NCDHW, or with flags = MVS_LAYOUT_CHANNELS_LAST
+ *                                       [batch][Iz][Iy][Ix][16]; in_size = {Iz, Iy, Ix} (HOST int[3])
+ *   gy  [batch][8][Oz][Oy][Ox]          NCDHW output gradient, read in place; out_size (HOST int[3])
+ *   dw  [16][8][3][3][3]                nn.ConvTranspose3d's weight layout
+ *   w27 [27][16][8]                     the weight as [tap][ci][co]
+ *   gx  x's layout (flags), every element written
+ * flags: 0 or MVS_LAYOUT_CHANNELS_LAST.  crop (HOST int[3]): every crop[k] >= 0, in_size[k] >= 1,
+ * out_size[k] >= 1; every device pointer contiguous fp32 with a 16-byte-aligned base.  Index width: batch * Iz *
+ * Iy * Ix and batch * Oz * Oy * Ox below 2^31, every in_size[k] and crop[k] below 2^29, and one sample of gy
+ * (8 * Oz * Oy * Ox floats) below 4 GB (else MVS_ERR_TOO_LARGE); gy as a whole may pass 4 GB.
+ *   wgrad: dw[ci][co][t] = sum over b and i of x[b][ci][i] * gy[b][co][2 i - crop + t]: fp32 on the f32-input
+ *          matrix cores, partial sums per workgroup reduced in a fixed order (bit-reproducible; no atomics; the
+ *          workspace need not be zeroed).  workspace:
+ *          mvs_deconv3d_k3s2_wgrad_workspace_bytes(batch, c_in, c_out, in_size, out_size) bytes (0 for arguments
+ *          the launch would refuse).
+ *   dgrad: gx[b][ci][i] = sum over t and co of gy[b][co][2 i - crop + t] * w[ci][co][t]: one output owner per
+ *          input voxel, three partial sums per output, one per tap plane tz, added once as (p0 + p1) + p2. */
+size_t mvs_deconv3d_k3s2_wgrad_workspace_bytes(int batch, int c_in, int c_out, const int* in_size,
+                                               const int* out_size);
+int mvs_deconv3d_k3s2_wgrad(const float* x, int flags, const float* gy, int batch, int c_in, int c_out,
+                            const int* in_size, const int* crop, const int* out_size, float* dw, float* workspace,
+                            void* stream);
+int mvs_deconv3d_k3s2_dgrad(const float* gy, const float* w27, int flags, int batch, int c_in, int c_out,
+                            const int* in_size, const int* crop, const int* out_size, float* gx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
