@@ -1110,4 +1110,58 @@ int mvs_bn_relu(const float* x, int layout, int batch, int channels, long long v
   return lc.status();
 }
 
+// ---- training extension: the train-mode BatchNorm + ReLU backward (bn_train_bwd.hip) ----
+namespace {
+// MVS_OK when the mvs_bn_relu_bwd_* launches can run on this geometry; box: the box's origin and size, or the
+// whole volume when both are null
+int bn_bwd_geometry(int layout, int batch, int channels, const int* dims, const int* box_origin,
+                    const int* box_size, int (&o)[3], int (&s)[3]) {
+  if (!dims || batch <= 0 || channels <= 0 || !both_or_neither(box_origin, box_size)) return MVS_ERR_INVALID_ARGUMENT;
+  if (!channel_layout_ok(layout, channels, nullptr, nullptr, nullptr)) return MVS_ERR_INVALID_ARGUMENT;
+  for (int k = 0; k < 3; ++k) {
+    if (dims[k] <= 0) return MVS_ERR_INVALID_ARGUMENT;
+    o[k] = box_origin ? box_origin[k] : 0;
+    s[k] = box_size ? box_size[k] : dims[k];
+    if (o[k] < 0 || s[k] <= 0 || s[k] > dims[k] || o[k] > dims[k] - s[k]) return MVS_ERR_INVALID_ARGUMENT;
+  }
+  if ((uint64_t)batch * channels > 65535u && !(layout & MVS_LAYOUT_CHANNELS_LAST)) return MVS_ERR_TOO_LARGE;
+  return MVS_OK;
+}
+}  // namespace
+
+size_t mvs_bn_relu_bwd_slots(int layout, int batch, int channels, const int* dims, const int* box_origin,
+                             const int* box_size) {
+  int o[3], s[3];
+  if (bn_bwd_geometry(layout, batch, channels, dims, box_origin, box_size, o, s) != MVS_OK) return 0;
+  return mvs::bn_relu_bwd_slots((layout & MVS_LAYOUT_CHANNELS_LAST) != 0, batch, channels, dims, s);
+}
+
+int mvs_bn_relu_bwd_reduce(const float* z, const float* gy, int layout, int batch, int channels, const int* dims,
+                           const int* box_origin, const int* box_size, const float* scale, const float* shift,
+                           const float* mean, double* stats, void* stream) {
+  if (!z || !gy || !scale || !shift || !mean || !stats) return MVS_ERR_INVALID_ARGUMENT;
+  if (((uintptr_t)z | (uintptr_t)gy) & 15u || (uintptr_t)stats & 7u) return MVS_ERR_INVALID_ARGUMENT;
+  int o[3], s[3];
+  const int st = bn_bwd_geometry(layout, batch, channels, dims, box_origin, box_size, o, s);
+  if (st != MVS_OK) return st;
+  const mvs::LaunchCheck lc;
+  mvs::launch_bn_relu_bwd_reduce(z, gy, (layout & MVS_LAYOUT_CHANNELS_LAST) != 0, batch, channels, dims, o, s, scale,
+                                 shift, mean, stats, (hipStream_t)stream);
+  return lc.status();
+}
+
+int mvs_bn_relu_bwd_apply(const float* z, const float* gy, int layout, int batch, int channels, const int* dims,
+                          const int* box_origin, const int* box_size, const float* scale, const float* shift,
+                          const float* mean, const float* g_s1, const float* g_s2, float* gz, void* stream) {
+  if (!z || !gy || !scale || !shift || !mean || !g_s1 || !g_s2 || !gz) return MVS_ERR_INVALID_ARGUMENT;
+  if (((uintptr_t)z | (uintptr_t)gy | (uintptr_t)gz) & 15u) return MVS_ERR_INVALID_ARGUMENT;
+  int o[3], s[3];
+  const int st = bn_bwd_geometry(layout, batch, channels, dims, box_origin, box_size, o, s);
+  if (st != MVS_OK) return st;
+  const mvs::LaunchCheck lc;
+  mvs::launch_bn_relu_bwd_apply(z, gy, (layout & MVS_LAYOUT_CHANNELS_LAST) != 0, batch, channels, dims, o, s, scale,
+                                shift, mean, g_s1, g_s2, gz, (hipStream_t)stream);
+  return lc.status();
+}
+
 }  // extern "C"

@@ -221,6 +221,18 @@ void launch_bn_relu(const float* x, bool channels_last, int B, int C, size_t vox
                     const float* sh, const float* mu, const float* r, const float* rsc, const float* rsh,
                     const float* rmu, float* y, uint32_t* y_bound, hipStream_t s);
 
+// bn_train_bwd.hip: the backward of out = relu(BN(z[box])) with the batch statistics over all of z
+// (mvs_bn_relu_bwd_*): n = z's extents, the box [o, o + s) inside them, gy contiguous on the box in z's layout.
+// reduce: stats[slot][2][C] = per-channel float64 (sum ga, sum ga z), ga = gy under the forward's ReLU mask, every
+// entry of the bn_relu_bwd_slots slots written once; apply: gz = ga * scale + g_s1 + 2 z g_s2 over all of z
+size_t bn_relu_bwd_slots(bool channels_last, int B, int C, const int* n, const int* s);
+void launch_bn_relu_bwd_reduce(const float* z, const float* gy, bool channels_last, int B, int C, const int* n,
+                               const int* o, const int* s, const float* sc, const float* sh, const float* mu,
+                               double* stats, hipStream_t st);
+void launch_bn_relu_bwd_apply(const float* z, const float* gy, bool channels_last, int B, int C, const int* n,
+                              const int* o, const int* s, const float* sc, const float* sh, const float* mu,
+                              const float* gs1, const float* gs2, float* gz, hipStream_t st);
+
 // dtu_input.hip: data.py:206-210 image normalisation (uint8 HWC -> fp32 NCHW), data.py:300-301
 // depth thresholds
 void launch_normalize_images(const uint8_t* rgb, int n, uint32_t hw, const float* mean3,

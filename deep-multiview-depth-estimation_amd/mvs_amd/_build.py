@@ -18,7 +18,8 @@ SOURCES = [os.path.join(CSRC, f) for f in ("capi.hip", "plane_sampling.hip", "co
                                            "conv3d_region_split.hip", "conv2d_split.hip",
                                            "conv3d_wgrad.hip", "conv3d_s2_lds.hip",
                                            "conv3d_region_wgrad.hip", "conv3d_s2_wgrad.hip",
-                                           "conv3d_t2_wgrad.hip", "deconv3d_region_bwd.hip")]
+                                           "conv3d_t2_wgrad.hip", "deconv3d_region_bwd.hip",
+                                           "bn_train_bwd.hip")]
 HEADERS = [os.path.join(REPO_ROOT, "include", "mvs_cost_volume.h"),
            os.path.join(REPO_ROOT, "include", "train", "mvs_region_train.h"),
            os.path.join(CSRC, "common.h"), os.path.join(CSRC, "launchers.h"),
@@ -29,8 +30,10 @@ HEADERS = [os.path.join(REPO_ROOT, "include", "mvs_cost_volume.h"),
 # a producer item's variance came out wrong in a schedule-dependent share of launches (0 to 100 % of
 # them across builds that only reorder the producer's instructions); the same builds without packed fp32:
 # 0.  Elementwise identical arithmetic (a packed FMA is two fmaf): the outputs keep
-# their bits.
-SOURCE_FLAGS = {"cv_head.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+# their bits.  The train-mode BN backward (bn_train_bwd.hip) is built the same way: its reduce kernels store to
+# LDS next to fp32 code the compiler would pair, the pattern above; they are HBM-bound, so it costs nothing.
+_NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+SOURCE_FLAGS = {"cv_head.hip": _NO_PACKED_FP32, "bn_train_bwd.hip": _NO_PACKED_FP32}
 OUTPUT = os.path.join(_HERE, "libmvs_cost_volume.so")
 ARCH = os.environ.get("MVS_OFFLOAD_ARCH", "gfx950")
 

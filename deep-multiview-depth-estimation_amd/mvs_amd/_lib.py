@@ -121,6 +121,9 @@ TRAIN_SIGNATURES = {
     "mvs_deconv3d_k3s2_wgrad_workspace_bytes": (ctypes.c_size_t, [_c_int, _c_int, _c_int, _p, _p]),
     "mvs_deconv3d_k3s2_wgrad": (_c_int, [_p, _c_int, _p, _c_int, _c_int, _c_int, _p, _p, _p, _p, _p, _p]),
     "mvs_deconv3d_k3s2_dgrad": (_c_int, [_p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p, _p]),
+    "mvs_bn_relu_bwd_slots": (ctypes.c_size_t, [_c_int, _c_int, _c_int, _p, _p, _p]),
+    "mvs_bn_relu_bwd_reduce": (_c_int, [_p, _p, _c_int, _c_int, _c_int] + [_p] * 8),
+    "mvs_bn_relu_bwd_apply": (_c_int, [_p, _p, _c_int, _c_int, _c_int] + [_p] * 10),
 }
 
 

@@ -1650,10 +1650,12 @@ def bn_train_params(bn, s1, s2, count, border=None):
     return params
 
 
-def bn_relu_(x: torch.Tensor, channels_last: bool, scale, shift, mean, r=None, r_bn=None, y_bound=None) -> torch.Tensor:
+def bn_relu_(x: torch.Tensor, channels_last: bool, scale, shift, mean, r=None, r_bn=None, y_bound=None,
+             out=None) -> torch.Tensor:
     """In place: x = relu((x - mean) * scale + shift) [+ relu(BN_r(r))], channels on the last dim
     (channels_last) or dim 1; r_bn = (scale, shift, mean) of r.  x must be contiguous fp32.
-    ``y_bound``: zeroed bound words raised to max of the result."""
+    ``y_bound``: zeroed bound words raised to max of the result.  ``out``: a contiguous fp32 tensor of x's shape
+    that takes the result instead (x is then only read; returns out)."""
     _require_gpu(x, "x")
     lib = _lib.load()
     if not x.is_contiguous() or x.dtype != _F32:
@@ -1662,6 +1664,10 @@ def bn_relu_(x: torch.Tensor, channels_last: bool, scale, shift, mean, r=None, r
     vox = x.numel() // (x.shape[0] * c)
     f = lambda t: t.to(device=x.device, dtype=_F32).contiguous()
     sc, sh, mu = f(scale), f(shift), f(mean)
+    if out is not None and (out.shape != x.shape or not out.is_contiguous() or out.dtype != _F32
+                            or out.device != x.device):
+        raise ValueError("out: a contiguous fp32 tensor of x's shape on its device")
+    y = x if out is None else out
     rr = rs = None
     if r is not None:
         rr = f(r)
@@ -1670,10 +1676,79 @@ def bn_relu_(x: torch.Tensor, channels_last: bool, scale, shift, mean, r=None, r
         rs = [f(t) for t in r_bn]
     rc = lib.mvs_bn_relu(_lib.ptr(x), _lib.MVS_LAYOUT_CHANNELS_LAST if channels_last else 0, x.shape[0], c, vox,
                          _lib.ptr(sc), _lib.ptr(sh), _lib.ptr(mu), _opt_ptr(rr),
-                         *(_opt_ptr(t) for t in (rs or (None, None, None))), _lib.ptr(x),
+                         *(_opt_ptr(t) for t in (rs or (None, None, None))), _lib.ptr(y),
                          _bound_ptr(y_bound), _lib.stream_handle(x.device))
     _lib.check(rc, "mvs_bn_relu")
-    return x
+    return y
+
+
+def _bn_bwd_args(z, gy, channels_last, box):
+    """(layout flag, B, C, dims, box origin, box size) of the mvs_bn_relu_bwd_* calls: z and gy contiguous fp32
+    memory, channels on the last dim (channels_last) or dim 1; box: None or inclusive (lo, hi) per dim."""
+    _require_gpu(z, "z")
+    _require_gpu(gy, "gy")
+    if z.dim() != 5 or gy.dim() != 5 or not (z.is_contiguous() and gy.is_contiguous()) or z.dtype != _F32 \
+            or gy.dtype != _F32:
+        raise ValueError("z and gy: contiguous 5-d fp32 tensors")
+    dims = tuple(z.shape[1:4] if channels_last else z.shape[2:])
+    have = tuple(gy.shape[1:4] if channels_last else gy.shape[2:])
+    size = dims if box is None else tuple(hi - lo + 1 for lo, hi in box)
+    c = z.shape[-1] if channels_last else z.shape[1]
+    if have != size or gy.shape[0] != z.shape[0] or (gy.shape[-1] if channels_last else gy.shape[1]) != c:
+        raise ValueError("gy %s is not z %s on the box %s" % (tuple(gy.shape), tuple(z.shape), box))
+    org = None if box is None else _ints3([lo for lo, _ in box])
+    return (_lib.MVS_LAYOUT_CHANNELS_LAST if channels_last else 0, z.shape[0], c, _ints3(dims), org,
+            None if box is None else _ints3(size))
+
+
+def bn_relu_bwd_slots(z, channels_last: bool, box=None) -> int:
+    """Slots (workgroups) of bn_relu_bwd_reduce for z and the box (mvs_bn_relu_bwd_slots); with box=None also the
+    grid of bn_relu_bwd_apply.  Shapes only: z may be a meta tensor."""
+    lib = _lib.load()
+    dims = tuple(z.shape[1:4] if channels_last else z.shape[2:])
+    c = z.shape[-1] if channels_last else z.shape[1]
+    org = None if box is None else _ints3([lo for lo, _ in box])
+    size = None if box is None else _ints3([hi - lo + 1 for lo, hi in box])
+    return int(lib.mvs_bn_relu_bwd_slots(_lib.MVS_LAYOUT_CHANNELS_LAST if channels_last else 0, z.shape[0], c,
+                                         _ints3(dims), org, size))
+
+
+def bn_relu_bwd_reduce(z, gy, channels_last: bool, box, scale, shift, mean, workspace=None):
+    """Pass 1 of the train-mode BN + ReLU backward (mvs_bn_relu_bwd_reduce, csrc/bn_train_bwd.hip): per channel,
+    float64 [C] each, S_g = sum ga and S_gz = sum ga * z over the box, ga = gy where the forward's
+    (z - mean) * scale + shift is positive.  Slot-owned partial sums added in a fixed order: bit-identical run to
+    run whatever ``workspace`` ([slots, 2, C] float64, allocated when None) held."""
+    layout, b, c, dims, org, size = _bn_bwd_args(z, gy, channels_last, box)
+    lib = _lib.load()
+    slots = lib.mvs_bn_relu_bwd_slots(layout, b, c, dims, org, size)
+    if slots == 0:
+        _lib.check(-1, "mvs_bn_relu_bwd_slots")
+    if workspace is None:
+        workspace = torch.empty((slots, 2, c), device=z.device, dtype=torch.float64)
+    elif tuple(workspace.shape) != (slots, 2, c) or workspace.dtype != torch.float64 or not workspace.is_contiguous():
+        raise ValueError("workspace: contiguous float64 [%d, 2, %d]" % (slots, c))
+    f = lambda t: t.to(device=z.device, dtype=_F32).contiguous()
+    sc, sh, mu = f(scale), f(shift), f(mean)
+    rc = lib.mvs_bn_relu_bwd_reduce(_lib.ptr(z), _lib.ptr(gy), layout, b, c, dims, org, size, _lib.ptr(sc),
+                                    _lib.ptr(sh), _lib.ptr(mu), _lib.ptr(workspace), _lib.stream_handle(z.device))
+    _lib.check(rc, "mvs_bn_relu_bwd_reduce")
+    s = workspace.sum(0)
+    return s[0], s[1]
+
+
+def bn_relu_bwd_apply(z, gy, channels_last: bool, box, scale, shift, mean, g_s1, g_s2) -> torch.Tensor:
+    """Pass 2 (mvs_bn_relu_bwd_apply): gz = ga * scale + g_s1 + 2 z g_s2 over all of z (ga = 0 outside the box),
+    fp32 in z's memory layout, every element written once."""
+    layout, b, c, dims, org, size = _bn_bwd_args(z, gy, channels_last, box)
+    lib = _lib.load()
+    f = lambda t: t.to(device=z.device, dtype=_F32).contiguous()
+    sc, sh, mu, g1, g2 = f(scale), f(shift), f(mean), f(g_s1), f(g_s2)
+    gz = torch.empty_like(z)
+    rc = lib.mvs_bn_relu_bwd_apply(_lib.ptr(z), _lib.ptr(gy), layout, b, c, dims, org, size, _lib.ptr(sc),
+                                   _lib.ptr(sh), _lib.ptr(mu), _lib.ptr(g1), _lib.ptr(g2), _lib.ptr(gz),
+                                   _lib.stream_handle(z.device))
+    _lib.check(rc, "mvs_bn_relu_bwd_apply")
+    return gz
 
 
 def softmax_depth(x: torch.Tensor) -> torch.Tensor:

@@ -405,8 +405,28 @@ class CostVolumeReg(nn.Module):
         count = bsz * n[0] * n[1] * n[2]
         if _hip_cv(cv):
             return self._forward_live_train_hip(cv, n, full, M, R1, R2, count, bound)
+        from . import bn_train
+        fused = bn_train.enabled(cv)
+
+        def site(z, bn, z_reg=None, box=None, extra=None, crop_first=True):
+            """One BN + ReLU site: (relu(BN(z)) on ``box`` of z's region z_reg -- all of z when None --, the BN's
+            (scale, shift, mean)); ``extra``: the border term added to the sums.  MVS_TRAIN_BN=hip: one autograd
+            node on the HIP kernels (bn_train.bn_relu_train); else the torch ops, the BN applied to the crop
+            (crop_first) or the crop taken from the BN's output."""
+            if fused:
+                rel = None if box is None else tuple((lo - zlo, hi - zlo) for (zlo, _), (lo, hi) in zip(z_reg, box))
+                return bn_train.bn_relu_train(z, rel, bn, extra, count)
+            s1, s2 = _sums(z)
+            if extra is not None:
+                s1, s2 = s1 + extra[0], s2 + extra[1]
+            p = _bn_train(bn, s1, s2, count)
+            if box is None:
+                return act(z, p), p
+            if crop_first:
+                return act(_crop_pad(z, z_reg, box, n), p), p
+            return _crop_pad(act(z, p), z_reg, box, n), p
         y0 = _narrow_conv(self.conv_0_0, cv)
-        y0 = act(y0, _bn_train(self.BN_0, *_sums(y0), count))
+        y0 = site(y0, self.BN_0)[0]
         stage = []
         convs_a = ((self.conv_1_0, self.BN_1), (self.conv_2_0, self.BN_2), (self.conv_3_0, self.BN_3))
         # the three stride-2 convs read the same volume over the same region R2: ONE convolution with their
@@ -415,24 +435,22 @@ class CostVolumeReg(nn.Module):
                              splits=tuple(c.weight.shape[0] for c, _ in convs_a))   # 0 outside M
         zs = zs.split([c.weight.shape[0] for c, _ in convs_a], 1)
         for z, (conv_a, bn) in zip(zs, convs_a):
-            p = _bn_train(bn, *_sums(z), count)
-            stage.append((act(z, p), _bn_constant(p)))              # relu(BN(0)) outside M
+            y, p = site(z, bn)
+            stage.append((y, _bn_constant(p)))                      # relu(BN(0)) outside M
         lv = []
         for (y, a), conv_b, bn in zip(stage, (self.conv_1_1, self.conv_2_1, self.conv_3_1),
                                       (self.BN_1, self.BN_2, self.BN_3)):
             z = _conv_s1_region(y, R2, conv_b.weight, R1, n)
-            s1, s2 = _sums(z)
-            c1, c2 = _border_class_sums(conv_b.weight, a, R1, n, bsz)
-            p = _bn_train(bn, s1 + c1, s2 + c2, count)
-            lv.append(_crop_pad(act(z, p), R1, M, n))
+            # (the torch ops apply the BN on R1 and crop; the fused node applies it on M: the same values)
+            lv.append(site(z, bn, R1, M, _border_class_sums(conv_b.weight, a, R1, n, bsz), crop_first=False)[0])
         y1, y2, y3 = lv
         # (the full outputs for the statistics; BN + ReLU on M only, the next layer's input)
         z = _tconv_region(y3, M, self.deconv_3_0.weight, full, self.pad, n)
-        y3 = act(_crop_pad(z, full, M, n), _bn_train(self.BN_2, *_sums(z), count))
+        y3 = site(z, self.BN_2, full, M)[0]
         z = _tconv_region(y3 + y2, M, self.deconv_2_0.weight, full, self.pad, n)
-        y2 = act(_crop_pad(z, full, M, n), _bn_train(self.BN_1, *_sums(z), count))
+        y2 = site(z, self.BN_1, full, M)[0]
         z = _tconv_region(y2 + y1, M, self.deconv_1_0.weight, full, self.pad)
-        z = act(z, _bn_train(self.BN_0, *_sums(z), count)) + y0
+        z = site(z, self.BN_0)[0] + y0
         return self.Norm(_narrow_conv(self.conv_out, z))
 
     def _forward_live_train_hip(self, cv, n, full, M, R1, R2, count, bound=None):

@@ -121,6 +121,34 @@ int mvs_deconv3d_k3s2_wgrad(const float* x, int flags, const float* gy, int batc
 int mvs_deconv3d_k3s2_dgrad(const float* gy, const float* w27, int flags, int batch, int c_in, int c_out,
                             const int* in_size, const int* crop, const int* out_size, float* gx, void* stream);
 
+/* Backward of a train-mode BatchNorm + ReLU site of the regulariser (mvs_amd/bn_train.py):
+ *   out = relu((z[box] - mean) * scale + shift), the batch statistics formed over ALL of z
+ * (forward: mvs_channel_stats, mvs_bn_relu on a copy of the box).  Two passes, each reading z and gy once:
+ *   reduce: ga = gy where (z - mean) * scale + shift > 0 -- mvs_bn_relu's expression and rounding, so the mask is
+ *           the forward's -- and 0 elsewhere; stats[slot][0][c] = sum ga, stats[slot][1][c] = sum ga * z over the
+ *           box, float64, one slot per workgroup written once and summed by the caller in slot order
+ *           (bit-reproducible; no atomics; stats need not be zeroed).  Slots:
+ *           mvs_bn_relu_bwd_slots(...) (0 for arguments the launch would refuse).
+ *   apply:  gz = ga * scale + g_s1 + 2 * z * g_s2 over all of z (ga = 0 outside the box), fp32, every element
+ *           written once; its grid is the reduce's for the whole volume (mvs_bn_relu_bwd_slots with a null box).
+ *   z, gz [batch][channels][D][H][W]        NCDHW, or with layout = MVS_LAYOUT_CHANNELS_LAST
+ *                                           [batch][D][H][W][channels]; dims = {D, H, W} (HOST int[3])
+ *   gy                                      z's layout on the box: [batch][channels][sz][sy][sx] or
+ *                                           [batch][sz][sy][sx][channels], contiguous
+ *   scale, shift, mean, g_s1, g_s2 [channels]   fp32 (mvs_bn_train_params' rows; the sums' gradients)
+ * box_origin, box_size (HOST int[3]): both null (the whole volume) or both given with 0 <= origin and
+ * origin + size <= dims, size >= 1 per dim.  Channels-last wants channels = 4 * a power of two <= 256; NCDHW
+ * wants batch * channels <= 65535 (else MVS_ERR_TOO_LARGE).  z, gy and gz contiguous fp32 with 16-byte-aligned
+ * bases; they may pass 4 GB (64-bit offsets). */
+size_t mvs_bn_relu_bwd_slots(int layout, int batch, int channels, const int* dims, const int* box_origin,
+                             const int* box_size);
+int mvs_bn_relu_bwd_reduce(const float* z, const float* gy, int layout, int batch, int channels, const int* dims,
+                           const int* box_origin, const int* box_size, const float* scale, const float* shift,
+                           const float* mean, double* stats, void* stream);
+int mvs_bn_relu_bwd_apply(const float* z, const float* gy, int layout, int batch, int channels, const int* dims,
+                          const int* box_origin, const int* box_size, const float* scale, const float* shift,
+                          const float* mean, const float* g_s1, const float* g_s2, float* gz, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
