@@ -151,6 +151,76 @@ int cost_volume_fwd_impl(const float* feat, const float* K, const float* R, cons
   return lc.status();
 }
 
+
+// ---- training extension (include/train/mvs_region_train.h): what its entry points share ----
+// every pointer non-null and 16-byte aligned
+template <class... P>
+bool aligned16(const P*... p) {
+  return (... && (p != nullptr)) && !((... | (uintptr_t)p) & 15u);
+}
+
+// MVS_OK when mvs_conv3d_region_wgrad can launch on this geometry
+int region_wgrad_geometry(int batch, int channels, const int* in_size) {
+  if (!in_size || batch <= 0 || !mvs::conv3d_region_wgrad_supported(channels)) return MVS_ERR_INVALID_ARGUMENT;
+  uint64_t vox = (uint64_t)batch;
+  for (int k = 0; k < 3; ++k) {
+    if (in_size[k] < 3) return MVS_ERR_INVALID_ARGUMENT;
+    vox *= (uint64_t)in_size[k];
+    if (vox >= (1ull << 31)) return MVS_ERR_TOO_LARGE;   // 32-bit row and tile indices
+  }
+  return MVS_OK;
+}
+
+// MVS_OK when the weight / input gradient of a stride-2 layer can launch: a coarse and a fine grid with fine
+// index 2 c - offset + t (the stride-2 convolution: its output box and the volume, offset = pad_lo; the transposed
+// ones: their input and the output box, offset = crop; null where the caller has none: not checked), gy on the
+// fine grid or the coarse one with gy_channels channels
+int stride2_bwd_geometry(int batch, const int* coarse, const int* fine, const int* offset, bool gy_fine,
+                         int gy_channels) {
+  if (!coarse || !fine || batch <= 0) return MVS_ERR_INVALID_ARGUMENT;
+  const int* gy_size = gy_fine ? fine : coarse;
+  uint64_t cvox = (uint64_t)batch, fvox = (uint64_t)batch, gy_sample = 1;
+  for (int k = 0; k < 3; ++k)
+    if (coarse[k] < 1 || fine[k] < 1 || (offset && offset[k] < 0)) return MVS_ERR_INVALID_ARGUMENT;
+  for (int k = 0; k < 3; ++k) {
+    cvox *= (uint64_t)coarse[k];
+    fvox *= (uint64_t)fine[k];
+    gy_sample *= (uint64_t)gy_size[k];
+    if (cvox >= (1ull << 31) || fvox >= (1ull << 31)) return MVS_ERR_TOO_LARGE;   // 32-bit row and voxel indices
+    // 2 c - offset + t in 32 bits (a coarse gy extent this long also fails the sample bound below: no status of
+    // the stride-2 convolution's entry points, which never tested it here, changes)
+    if (coarse[k] >= (1 << 29) || (offset && offset[k] >= (1 << 29))) return MVS_ERR_TOO_LARGE;
+  }
+  // one sample of gy behind one 32-bit buffer descriptor (the input gradient's loads)
+  if (gy_sample * (uint64_t)gy_channels * sizeof(float) >= 0xFFFFFFC0ull) return MVS_ERR_TOO_LARGE;
+  return MVS_OK;
+}
+
+int s2_region_bwd_geometry(int batch, const int* dims, const int* pad_lo, const int* out_size) {
+  return stride2_bwd_geometry(batch, out_size, dims, pad_lo, false, 112);
+}
+
+int t2_region_bwd_geometry(int batch, int c_in, int c_out, const int* in_size, const int* crop, const int* out_size) {
+  if (!mvs::conv3d_t2_wgrad_supported(c_in, c_out)) return MVS_ERR_INVALID_ARGUMENT;
+  return stride2_bwd_geometry(batch, in_size, out_size, crop, true, c_out);
+}
+
+int deconv3d_bwd_geometry(int batch, int c_in, int c_out, const int* in_size, const int* crop, const int* out_size) {
+  if (c_in != 16 || c_out != 8) return MVS_ERR_INVALID_ARGUMENT;
+  return stride2_bwd_geometry(batch, in_size, out_size, crop, true, c_out);
+}
+
+// the entry points' prologue and epilogue: `ok` (pointers, flags), then the geometry's status, then (the input
+// gradients: grid.z) the batch bound, then the launch under a LaunchCheck
+template <class Launch>
+int train_launch(bool ok, int geometry, bool batch_in_grid_z, int batch, Launch&& launch) {
+  if (!ok) return MVS_ERR_INVALID_ARGUMENT;
+  if (geometry != MVS_OK) return geometry;
+  if (batch_in_grid_z && batch > 65535) return MVS_ERR_TOO_LARGE;
+  const mvs::LaunchCheck lc;
+  const int ls = launch();
+  return ls != MVS_OK ? ls : lc.status();
+}
 }  // namespace
 
 extern "C" {
@@ -628,20 +698,6 @@ int mvs_conv3d_k3_wgrad(const float* x, const float* gy, int batch, int c_in, in
 // ---- training extension (include/train/mvs_region_train.h) ----
 int mvs_train_abi_version(void) { return MVS_TRAIN_ABI_VERSION; }
 
-namespace {
-// MVS_OK when mvs_conv3d_region_wgrad can launch on this geometry
-int region_wgrad_geometry(int batch, int channels, const int* in_size) {
-  if (!in_size || batch <= 0 || !mvs::conv3d_region_wgrad_supported(channels)) return MVS_ERR_INVALID_ARGUMENT;
-  uint64_t vox = (uint64_t)batch;
-  for (int k = 0; k < 3; ++k) {
-    if (in_size[k] < 3) return MVS_ERR_INVALID_ARGUMENT;
-    vox *= (uint64_t)in_size[k];
-    if (vox >= (1ull << 31)) return MVS_ERR_TOO_LARGE;   // 32-bit row and tile indices
-  }
-  return MVS_OK;
-}
-}  // namespace
-
 size_t mvs_conv3d_region_wgrad_workspace_bytes(int batch, int channels, const int* in_size) {
   if (region_wgrad_geometry(batch, channels, in_size) != MVS_OK) return 0;
   return mvs::conv3d_region_wgrad_workspace_bytes(batch, channels, in_size);
@@ -649,34 +705,13 @@ size_t mvs_conv3d_region_wgrad_workspace_bytes(int batch, int channels, const in
 
 int mvs_conv3d_region_wgrad(const float* x, const float* gy, int batch, int channels, const int* in_size,
                             float* dw, float* workspace, void* stream) {
-  if (!x || !gy || !dw || !workspace) return MVS_ERR_INVALID_ARGUMENT;
-  if (((uintptr_t)x | (uintptr_t)gy | (uintptr_t)dw | (uintptr_t)workspace) & 15u) return MVS_ERR_INVALID_ARGUMENT;
-  const int st = region_wgrad_geometry(batch, channels, in_size);
-  if (st != MVS_OK) return st;
-  const mvs::LaunchCheck lc;
-  mvs::launch_conv3d_region_wgrad(x, gy, batch, channels, in_size, workspace, dw, (hipStream_t)stream);
-  return lc.status();
+  return train_launch(aligned16(x, gy, dw, workspace), region_wgrad_geometry(batch, channels, in_size), false, batch,
+                      [&] {
+                        mvs::launch_conv3d_region_wgrad(x, gy, batch, channels, in_size, workspace, dw,
+                                                        (hipStream_t)stream);
+                        return MVS_OK;
+                      });
 }
-
-namespace {
-// MVS_OK when mvs_conv3d_s2_region_wgrad / _dgrad can launch on this geometry
-int s2_region_bwd_geometry(int batch, const int* dims, const int* pad_lo, const int* out_size) {
-  if (!dims || !out_size || batch <= 0) return MVS_ERR_INVALID_ARGUMENT;
-  uint64_t vox = (uint64_t)batch, ovox = (uint64_t)batch, osample = 1;
-  for (int k = 0; k < 3; ++k)
-    if (dims[k] < 1 || out_size[k] < 1 || (pad_lo && pad_lo[k] < 0)) return MVS_ERR_INVALID_ARGUMENT;
-  for (int k = 0; k < 3; ++k) {
-    vox *= (uint64_t)dims[k];
-    ovox *= (uint64_t)out_size[k];
-    osample *= (uint64_t)out_size[k];
-    if (vox >= (1ull << 31) || ovox >= (1ull << 31)) return MVS_ERR_TOO_LARGE;   // 32-bit row and voxel indices
-    if (pad_lo && pad_lo[k] >= (1 << 29)) return MVS_ERR_TOO_LARGE;               // 2 o - pad_lo + t in 32 bits
-  }
-  // one sample of gy behind one 32-bit buffer descriptor (the input gradient's loads)
-  if (osample * 112u * sizeof(float) >= 0xFFFFFFC0ull) return MVS_ERR_TOO_LARGE;
-  return MVS_OK;
-}
-}  // namespace
 
 size_t mvs_conv3d_s2_region_wgrad_workspace_bytes(int batch, const int* dims, const int* out_size) {
   if (s2_region_bwd_geometry(batch, dims, nullptr, out_size) != MVS_OK) return 0;
@@ -685,47 +720,22 @@ size_t mvs_conv3d_s2_region_wgrad_workspace_bytes(int batch, const int* dims, co
 
 int mvs_conv3d_s2_region_wgrad(const float* x, const float* gy, int batch, const int* dims, const int* pad_lo,
                                const int* out_size, float* dw, float* workspace, void* stream) {
-  if (!x || !gy || !dw || !workspace || !pad_lo) return MVS_ERR_INVALID_ARGUMENT;
-  if (((uintptr_t)x | (uintptr_t)gy | (uintptr_t)dw | (uintptr_t)workspace) & 15u) return MVS_ERR_INVALID_ARGUMENT;
-  const int st = s2_region_bwd_geometry(batch, dims, pad_lo, out_size);
-  if (st != MVS_OK) return st;
-  const mvs::LaunchCheck lc;
-  mvs::launch_conv3d_s2_wgrad(x, gy, batch, dims, pad_lo, out_size, workspace, dw, (hipStream_t)stream);
-  return lc.status();
+  return train_launch(aligned16(x, gy, dw, workspace) && pad_lo, s2_region_bwd_geometry(batch, dims, pad_lo, out_size),
+                      false, batch, [&] {
+                        mvs::launch_conv3d_s2_wgrad(x, gy, batch, dims, pad_lo, out_size, workspace, dw,
+                                                    (hipStream_t)stream);
+                        return MVS_OK;
+                      });
 }
 
 int mvs_conv3d_s2_region_dgrad(const float* gy, const float* w27, int batch, const int* dims, const int* pad_lo,
                                const int* out_size, float* gx, void* stream) {
-  if (!gy || !w27 || !gx || !pad_lo) return MVS_ERR_INVALID_ARGUMENT;
-  if (((uintptr_t)gy | (uintptr_t)w27 | (uintptr_t)gx) & 15u) return MVS_ERR_INVALID_ARGUMENT;
-  const int st = s2_region_bwd_geometry(batch, dims, pad_lo, out_size);
-  if (st != MVS_OK) return st;
-  if (batch > 65535) return MVS_ERR_TOO_LARGE;   // grid.z
-  const mvs::LaunchCheck lc;
-  mvs::launch_conv3d_s2_dgrad(gy, w27, gx, batch, dims, pad_lo, out_size, (hipStream_t)stream);
-  return lc.status();
+  return train_launch(aligned16(gy, w27, gx) && pad_lo, s2_region_bwd_geometry(batch, dims, pad_lo, out_size), true,
+                      batch, [&] {
+                        mvs::launch_conv3d_s2_dgrad(gy, w27, gx, batch, dims, pad_lo, out_size, (hipStream_t)stream);
+                        return MVS_OK;
+                      });
 }
-
-namespace {
-// MVS_OK when mvs_conv3d_t2_region_wgrad / _dgrad can launch on this geometry
-int t2_region_bwd_geometry(int batch, int c_in, int c_out, const int* in_size, const int* crop, const int* out_size) {
-  if (!in_size || !out_size || batch <= 0 || !mvs::conv3d_t2_wgrad_supported(c_in, c_out))
-    return MVS_ERR_INVALID_ARGUMENT;
-  uint64_t vox = (uint64_t)batch, ovox = (uint64_t)batch, osample = 1;
-  for (int k = 0; k < 3; ++k)
-    if (in_size[k] < 1 || out_size[k] < 1 || (crop && crop[k] < 0)) return MVS_ERR_INVALID_ARGUMENT;
-  for (int k = 0; k < 3; ++k) {
-    vox *= (uint64_t)in_size[k];
-    ovox *= (uint64_t)out_size[k];
-    osample *= (uint64_t)out_size[k];
-    if (vox >= (1ull << 31) || ovox >= (1ull << 31)) return MVS_ERR_TOO_LARGE;   // 32-bit row and voxel indices
-    if (in_size[k] >= (1 << 29) || (crop && crop[k] >= (1 << 29))) return MVS_ERR_TOO_LARGE;   // 2 i - crop + t
-  }
-  // one sample of gy behind one 32-bit buffer descriptor (the input gradient's loads)
-  if (osample * (uint64_t)c_out * sizeof(float) >= 0xFFFFFFC0ull) return MVS_ERR_TOO_LARGE;
-  return MVS_OK;
-}
-}  // namespace
 
 size_t mvs_conv3d_t2_region_wgrad_workspace_bytes(int batch, int c_in, int c_out, const int* in_size,
                                                   const int* out_size) {
@@ -735,46 +745,22 @@ size_t mvs_conv3d_t2_region_wgrad_workspace_bytes(int batch, int c_in, int c_out
 
 int mvs_conv3d_t2_region_wgrad(const float* x, const float* gy, int batch, int c_in, int c_out, const int* in_size,
                                const int* crop, const int* out_size, float* dw, float* workspace, void* stream) {
-  if (!x || !gy || !dw || !workspace || !crop) return MVS_ERR_INVALID_ARGUMENT;
-  if (((uintptr_t)x | (uintptr_t)gy | (uintptr_t)dw | (uintptr_t)workspace) & 15u) return MVS_ERR_INVALID_ARGUMENT;
-  const int st = t2_region_bwd_geometry(batch, c_in, c_out, in_size, crop, out_size);
-  if (st != MVS_OK) return st;
-  const mvs::LaunchCheck lc;
-  mvs::launch_conv3d_t2_wgrad(x, gy, batch, c_in, c_out, in_size, crop, out_size, workspace, dw, (hipStream_t)stream);
-  return lc.status();
+  return train_launch(aligned16(x, gy, dw, workspace) && crop,
+                      t2_region_bwd_geometry(batch, c_in, c_out, in_size, crop, out_size), false, batch, [&] {
+                        mvs::launch_conv3d_t2_wgrad(x, gy, batch, c_in, c_out, in_size, crop, out_size, workspace, dw,
+                                                    (hipStream_t)stream);
+                        return MVS_OK;
+                      });
 }
 
 int mvs_conv3d_t2_region_dgrad(const float* gy, const float* w27, int batch, int c_in, int c_out, const int* in_size,
                                const int* crop, const int* out_size, float* gx, void* stream) {
-  if (!gy || !w27 || !gx || !crop) return MVS_ERR_INVALID_ARGUMENT;
-  if (((uintptr_t)gy | (uintptr_t)w27 | (uintptr_t)gx) & 15u) return MVS_ERR_INVALID_ARGUMENT;
-  const int st = t2_region_bwd_geometry(batch, c_in, c_out, in_size, crop, out_size);
-  if (st != MVS_OK) return st;
-  if (batch > 65535) return MVS_ERR_TOO_LARGE;   // grid.z
-  const mvs::LaunchCheck lc;
-  const int ls = mvs::launch_conv3d_t2_dgrad(gy, w27, gx, batch, c_in, c_out, in_size, crop, out_size,
-                                             (hipStream_t)stream);
-  return ls != MVS_OK ? ls : lc.status();
+  return train_launch(aligned16(gy, w27, gx) && crop,
+                      t2_region_bwd_geometry(batch, c_in, c_out, in_size, crop, out_size), true, batch, [&] {
+                        return mvs::launch_conv3d_t2_dgrad(gy, w27, gx, batch, c_in, c_out, in_size, crop, out_size,
+                                                           (hipStream_t)stream);
+                      });
 }
-
-namespace {
-// MVS_OK when mvs_deconv3d_k3s2_wgrad / _dgrad can launch on this geometry
-int deconv3d_bwd_geometry(int batch, int c_in, int c_out, const int* in_size, const int* crop, const int* out_size) {
-  if (!in_size || !out_size || batch <= 0 || c_in != 16 || c_out != 8) return MVS_ERR_INVALID_ARGUMENT;
-  uint64_t vox = (uint64_t)batch, ovox = (uint64_t)batch, osample = 1;
-  for (int k = 0; k < 3; ++k)
-    if (in_size[k] < 1 || out_size[k] < 1 || (crop && crop[k] < 0)) return MVS_ERR_INVALID_ARGUMENT;
-  for (int k = 0; k < 3; ++k) {
-    vox *= (uint64_t)in_size[k];
-    ovox *= (uint64_t)out_size[k];
-    osample *= (uint64_t)out_size[k];
-    if (vox >= (1ull << 31) || ovox >= (1ull << 31)) return MVS_ERR_TOO_LARGE;   // 32-bit row and voxel indices
-    if (in_size[k] >= (1 << 29) || (crop && crop[k] >= (1 << 29))) return MVS_ERR_TOO_LARGE;   // 2 i - crop + t
-  }
-  if (osample * (uint64_t)c_out * sizeof(float) >= 0xFFFFFFC0ull) return MVS_ERR_TOO_LARGE;   // one sample of gy
-  return MVS_OK;
-}
-}  // namespace
 
 size_t mvs_deconv3d_k3s2_wgrad_workspace_bytes(int batch, int c_in, int c_out, const int* in_size,
                                                const int* out_size) {
@@ -785,28 +771,22 @@ size_t mvs_deconv3d_k3s2_wgrad_workspace_bytes(int batch, int c_in, int c_out, c
 int mvs_deconv3d_k3s2_wgrad(const float* x, int flags, const float* gy, int batch, int c_in, int c_out,
                             const int* in_size, const int* crop, const int* out_size, float* dw, float* workspace,
                             void* stream) {
-  if (!x || !gy || !dw || !workspace || !crop) return MVS_ERR_INVALID_ARGUMENT;
-  if (((uintptr_t)x | (uintptr_t)gy | (uintptr_t)dw | (uintptr_t)workspace) & 15u) return MVS_ERR_INVALID_ARGUMENT;
-  if (flags & ~MVS_LAYOUT_CHANNELS_LAST) return MVS_ERR_INVALID_ARGUMENT;
-  const int st = deconv3d_bwd_geometry(batch, c_in, c_out, in_size, crop, out_size);
-  if (st != MVS_OK) return st;
-  const mvs::LaunchCheck lc;
-  mvs::launch_deconv3d_wgrad(x, (flags & MVS_LAYOUT_CHANNELS_LAST) != 0, gy, batch, in_size, crop, out_size, workspace,
-                             dw, (hipStream_t)stream);
-  return lc.status();
+  return train_launch(aligned16(x, gy, dw, workspace) && crop && !(flags & ~MVS_LAYOUT_CHANNELS_LAST),
+                      deconv3d_bwd_geometry(batch, c_in, c_out, in_size, crop, out_size), false, batch, [&] {
+                        mvs::launch_deconv3d_wgrad(x, (flags & MVS_LAYOUT_CHANNELS_LAST) != 0, gy, batch, in_size, crop,
+                                                   out_size, workspace, dw, (hipStream_t)stream);
+                        return MVS_OK;
+                      });
 }
 
 int mvs_deconv3d_k3s2_dgrad(const float* gy, const float* w27, int flags, int batch, int c_in, int c_out,
                             const int* in_size, const int* crop, const int* out_size, float* gx, void* stream) {
-  if (!gy || !w27 || !gx || !crop) return MVS_ERR_INVALID_ARGUMENT;
-  if (((uintptr_t)gy | (uintptr_t)w27 | (uintptr_t)gx) & 15u) return MVS_ERR_INVALID_ARGUMENT;
-  if (flags & ~MVS_LAYOUT_CHANNELS_LAST) return MVS_ERR_INVALID_ARGUMENT;
-  const int st = deconv3d_bwd_geometry(batch, c_in, c_out, in_size, crop, out_size);
-  if (st != MVS_OK) return st;
-  const mvs::LaunchCheck lc;
-  mvs::launch_deconv3d_dgrad(gy, w27, gx, (flags & MVS_LAYOUT_CHANNELS_LAST) != 0, batch, in_size, crop, out_size,
-                             (hipStream_t)stream);
-  return lc.status();
+  return train_launch(aligned16(gy, w27, gx) && crop && !(flags & ~MVS_LAYOUT_CHANNELS_LAST),
+                      deconv3d_bwd_geometry(batch, c_in, c_out, in_size, crop, out_size), false, batch, [&] {
+                        mvs::launch_deconv3d_dgrad(gy, w27, gx, (flags & MVS_LAYOUT_CHANNELS_LAST) != 0, batch, in_size,
+                                                   crop, out_size, (hipStream_t)stream);
+                        return MVS_OK;
+                      });
 }
 
 int mvs_conv_head_fp32_fwd(const float* cv4, int batch, int d, int h, int w, const float* w0_wz,

@@ -1,45 +1,37 @@
 // conv3d_s2_wgrad.hip -- weight gradient of the regulariser's stacked stride-2 region convolution under
 // autograd (conv_1_0 / conv_2_0 / conv_3_0, model.py:101-107: Conv3d(32, 16 + 32 + 64, 3, stride 2) of the
-// whole cost volume on an output box; mvs_amd/region_train.py _S2Box), on the f32-input matrix cores.
+// whole cost volume on an output box; mvs_amd/region_train.py _S2Box), on wgrad_taprow.h's plan.
 //
 //   dW[co][ci][t] = sum over the batch and every output voxel o of gy[b][o][co] * x[b][2 o - pad_lo + t][ci]
 //
 // (terms off the volume are 0) with x the contiguous NCDHW volume [B][32][D][H][W], read in place, and gy
 // channels-last [B][Oz][Oy][Ox][112] is, per tap t, a 112 x 32 GEMM with K = the output voxels: 7 x 2
-// accumulator blocks.  As in conv3d_region_wgrad.hip the 27 taps are partitioned over workgroups by tap row
-// (tz, ty) -- a workgroup owns the row's three x taps, 3 x 7 x 2 MFMA blocks over its four waves: wave =
-// (ci block, co blocks 0-3 or 4-6), 12 or 9 accumulators -- and a workgroup is persistent over a K chunk: it
-// walks tiles of kSwTR output rows (flattened b, oz, oy) x 16 output x-voxels and keeps the accumulators in
-// registers across every tile of the chunk.  Per tile it stages in LDS, once,
-//   gy: kSwTR x 16 voxel records of 112 floats (one 16-byte global load per 4 channels); 112 = 48 mod 64, so
-//       the 4 voxels x 16 channels of an MFMA operand read land on 64 distinct banks without padding;
+// accumulator blocks.  A workgroup's tap row is 3 x 7 x 2 MFMA blocks over its four waves: wave = (ci block, co
+// blocks 0-3 or 4-6), 12 or 9 accumulators.  A tile is kSwTR output rows (flattened b, oz, oy); per tile it stages
+//   gy: kSwTR x 16 voxel records of 112 floats; 112 = 48 mod 64, so the 4 voxels x 16 channels of an MFMA operand
+//       read land on 64 distinct banks without padding;
 //   x:  the tap row's input row (b, 2 oz - pz + tz, 2 oy - py + ty) of each output row, the 33 inputs
 //       2 x0 - px + j along x, TRANSPOSED from NCDHW into voxel records of 32 + 16 floats (per channel plane
-//       16-byte loads along W, four scalar LDS stores) and laid out BY PARITY of j: 17 even then 17 odd
-//       records, so the four output voxels of a K-step (inputs two apart) read adjacent records -- tap tx = 0
-//       even record k, tx = 1 odd record k, tx = 2 even record k + 1 -- and with 48 floats per record an
+//       16-byte loads along W, four scalar LDS stores) in the header's parity order; with 48 floats per record an
 //       operand read again covers 64 distinct banks.
 // Output rows whose input row is off the volume are skipped (their products are all 0).  LDS: 68,560 B per
-// workgroup, two workgroups per CU (137 KB of 160 KB).  Each wave stores its blocks into the chunk's partial
-// [27][112][32] slot -- every slot entry is written exactly once per launch, none relies on a zeroed workspace
-// -- and conv3d_s2_wgrad_reduce_kernel sums the slots in slot order (deterministic, no atomics).  Products and
-// sums are fp32 (each MFMA step an fmaf chain).  Addresses into x are 64-bit (sample base + channel plane +
-// row): a sample's byte offset passes 2^31 at the training shapes.
+// workgroup, two workgroups per CU (137 KB of 160 KB).  Addresses into x are 64-bit (sample base + channel plane
+// + row): a sample's byte offset passes 2^31 at the training shapes.
+//
+// This kernel keeps its tile walk, row-offset table, staging and slot store inline (the header's plan, statement
+// for statement): through taprow_walk and the header's staging it measured 1.6 % slower at the training shape
+// (8.05 against 7.92 ms), outside the parent's 0.3 % run-to-run spread.  It shares the header's constants, host
+// geometry, K-step and reduce; a change of the walk in wgrad_taprow.h has to be repeated here.
 #include "launchers.h"
-#include "packed.h"
+#include "wgrad_taprow.h"
 
 namespace mvs {
 namespace {
 
 constexpr int kSwCI = 32, kSwCO = 112;
-constexpr int kSwTX = 16;                       // output x-voxels of a tile
-constexpr int kSwHX = kSwTX + 1;                // staged x records per parity (even: taps 0 and 2)
-constexpr int kSwXR = 2 * kSwHX;                // staged x records per row
 constexpr int kSwTR = 5;                        // output rows per tile
 constexpr int kSwPG = kSwCO, kSwPX = kSwCI + 16;   // floats per staged gy / x record
-constexpr int kSwGV = kSwTR * kSwTX, kSwXV = kSwTR * kSwXR;
-constexpr int kSwChunks = 168;                  // K chunks: x 9 tap rows = 1512 workgroups, just under 3 rounds of
-                                                // the 512 that fit 256 CUs at two per CU
+constexpr int kSwGV = kSwTR * kTapRowTX, kSwXV = kSwTR * kTapRowFR;
 constexpr int kSwSlot = 27 * kSwCO * kSwCI;     // floats per partial slot
 static_assert((kSwGV * kSwPG + kSwXV * kSwPX) * 4 + 2 * kSwTR * 8 <= 80 * 1024, "two workgroups per CU");
 
@@ -47,8 +39,7 @@ struct SwGeo {
   int B, D, H, W;        // the volume x
   int Oz, Oy, Ox;        // gy's box
   int pz, py, px;        // pad_lo
-  int rows;              // B * Oz * Oy output rows
-  int tiles_x, tiles;    // x tiles per row group, tiles in all
+  TapRowGeo t;           // rows: B * Oz * Oy output rows
 };
 
 // the K-steps of one staged tile for a wave with NCB co blocks
@@ -58,20 +49,7 @@ __device__ __forceinline__ void sw_tile(const float* gys, const float* xs, const
 #pragma unroll 1
   for (int r = 0; r < kSwTR; ++r) {
     if (rowx[r] < 0) continue;   // workgroup-uniform: no such row, or its input row is off the volume
-#pragma unroll
-    for (int s = 0; s < kSwTX / 4; ++s) {
-      float a[NCB], bv[3];
-#pragma unroll
-      for (int c = 0; c < NCB; ++c) a[c] = gys[(r * kSwTX + 4 * s) * kSwPG + aoff + c * 16];
-      bv[0] = xs[(r * kSwXR + 4 * s) * kSwPX + boff];
-      bv[1] = xs[(r * kSwXR + kSwHX + 4 * s) * kSwPX + boff];
-      bv[2] = xs[(r * kSwXR + 4 * s + 1) * kSwPX + boff];
-#pragma unroll
-      for (int tx = 0; tx < 3; ++tx)
-#pragma unroll
-        for (int c = 0; c < NCB; ++c)
-          acc[tx][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c], bv[tx], acc[tx][c], 0, 0, 0);
-    }
+    taprow_ksteps<2, NCB, kSwPG, kSwPX>(gys + r * kTapRowTX * kSwPG + aoff, xs + r * kTapRowFR * kSwPX + boff, acc);
   }
 }
 
@@ -100,14 +78,14 @@ __global__ __launch_bounds__(kBlock) void conv3d_s2_wgrad_kernel(const float* __
 #pragma unroll
     for (int c = 0; c < 4; ++c) acc[tx][c] = f4v{0.0f, 0.0f, 0.0f, 0.0f};
 
-  for (int tile = chunk; tile < g.tiles; tile += chunks) {   // workgroup-uniform
-    const int x0 = (tile % g.tiles_x) * kSwTX, row0 = (tile / g.tiles_x) * kSwTR;
+  for (int tile = chunk; tile < g.t.tiles; tile += chunks) {   // workgroup-uniform
+    const int x0 = (tile % g.t.tiles_x) * kTapRowTX, row0 = (tile / g.t.tiles_x) * kSwTR;
     const int ix0 = 2 * x0 - g.px;   // the tile's first input along x (may be negative)
     __syncthreads();   // the previous tile's operand reads are done
     if (tid < kSwTR) {
       const int R = row0 + tid;
       long long og = -1, ox = -1;
-      if (R < g.rows) {
+      if (R < g.t.rows) {
         const int oy = R % g.Oy, t = R / g.Oy;
         const int oz = t % g.Oz, b = t / g.Oz;
         const int iz = 2 * oz - g.pz + tz, iy = 2 * oy - g.py + ty;
@@ -123,7 +101,7 @@ __global__ __launch_bounds__(kBlock) void conv3d_s2_wgrad_kernel(const float* __
     // box read 0 (their products vanish)
     for (int e = tid; e < kSwGV * Q; e += kBlock) {
       const int c4 = e % Q, v = e / Q;
-      const int r = v / kSwTX, xi = v % kSwTX;
+      const int r = v / kTapRowTX, xi = v % kTapRowTX;
       if (rowx[r] < 0) continue;
       f4v val{0.0f, 0.0f, 0.0f, 0.0f};
       if (x0 + xi < g.Ox)
@@ -147,12 +125,12 @@ __global__ __launch_bounds__(kBlock) void conv3d_s2_wgrad_kernel(const float* __
         for (int i = 0; i < 4; ++i)
           if (ix + i >= 0 && ix + i < g.W) val[i] = src[ix + i];
       }
-      float* dst = xs + (r * kSwXR + 2 * q) * kSwPX + ci;   // even record 2 q
+      float* dst = xs + (r * kTapRowFR + 2 * q) * kSwPX + ci;   // even record 2 q
       dst[0] = val[0];
-      dst[kSwHX * kSwPX] = val[1];
+      dst[kTapRowHX * kSwPX] = val[1];
       if (q < XQ - 1) {   // (j = 34, 35 are no tap of the tile)
         dst[kSwPX] = val[2];
-        dst[(kSwHX + 1) * kSwPX] = val[3];
+        dst[(kTapRowHX + 1) * kSwPX] = val[3];
       }
     }
     __syncthreads();
@@ -172,44 +150,27 @@ __global__ __launch_bounds__(kBlock) void conv3d_s2_wgrad_kernel(const float* __
     }
 }
 
-// dW[co][ci][t] = the slots' [t][co][ci] entries summed in slot order (fixed: deterministic)
-__global__ __launch_bounds__(kBlock) void conv3d_s2_wgrad_reduce_kernel(const float* __restrict__ part, int slots,
-                                                                       float* __restrict__ dw) {
-  const int i = (int)(blockIdx.x * kBlock + threadIdx.x);   // (t, co, ci): consecutive lanes, consecutive ci
-  if (i >= kSwSlot) return;
-  float s = 0.0f;
-  for (int k = 0; k < slots; ++k) s += part[(size_t)k * kSwSlot + i];
-  const int ci = i % kSwCI, co = (i / kSwCI) % kSwCO, t = i / (kSwCI * kSwCO);
-  dw[((size_t)co * kSwCI + ci) * 27 + t] = s;
-}
-
 SwGeo sw_geo(int B, const int* n, const int* pad_lo, const int* out) {
   SwGeo g;
   g.B = B;
   g.D = n[0], g.H = n[1], g.W = n[2];
   g.Oz = out[0], g.Oy = out[1], g.Ox = out[2];
   g.pz = pad_lo ? pad_lo[0] : 0, g.py = pad_lo ? pad_lo[1] : 0, g.px = pad_lo ? pad_lo[2] : 0;
-  g.rows = B * g.Oz * g.Oy;
-  g.tiles_x = (g.Ox + kSwTX - 1) / kSwTX;
-  g.tiles = g.tiles_x * ((g.rows + kSwTR - 1) / kSwTR);
+  g.t = taprow_geo(B * g.Oz * g.Oy, g.Ox, kSwTR);
   return g;
 }
-
-int sw_slots(const SwGeo& g) { return g.tiles < kSwChunks ? g.tiles : kSwChunks; }
 
 }  // namespace
 
 size_t conv3d_s2_wgrad_workspace_bytes(int B, const int* n, const int* out) {
-  return (size_t)sw_slots(sw_geo(B, n, nullptr, out)) * kSwSlot * sizeof(float);
+  return taprow_workspace_bytes(sw_geo(B, n, nullptr, out).t, 1, kSwSlot);
 }
 
 void launch_conv3d_s2_wgrad(const float* x, const float* gy, int B, const int* n, const int* pad_lo, const int* out,
                             float* part, float* dw, hipStream_t s) {
   const SwGeo g = sw_geo(B, n, pad_lo, out);
-  const int slots = sw_slots(g);
-  hipLaunchKernelGGL(conv3d_s2_wgrad_kernel, dim3(9u * (unsigned)slots), dim3(kBlock), 0, s, x, gy, part, g);
-  hipLaunchKernelGGL(conv3d_s2_wgrad_reduce_kernel, dim3((kSwSlot + kBlock - 1) / kBlock), dim3(kBlock), 0, s, part,
-                     slots, dw);
+  hipLaunchKernelGGL(conv3d_s2_wgrad_kernel, taprow_grid(g.t), dim3(kBlock), 0, s, x, gy, part, g);
+  launch_wgrad_reduce(part, taprow_chunks(g.t), kSwCO, kSwCI, dw, s);
 }
 
 }  // namespace mvs

@@ -16,23 +16,19 @@
 // the weights as workgroup-uniform scalar loads (deconv3d_region.hip's scheme); the three planes' sums are added
 // once as (p0 + p1) + p2.
 //
-// Weight gradient: on the f32-input matrix cores, conv3d_t2_wgrad.hip's plan.  The 27 taps are partitioned over
-// workgroups by tap row (tz, ty); a workgroup is persistent over a K chunk: it walks tiles of kDwTR coarse rows
-// (flattened b, iz, iy) x 16 coarse x-voxels and keeps its accumulators in registers across every tile of the
-// chunk.  Wave kp runs the rows kp, kp + 4, ... of each tile (four partial sums of K, a slot each).  Per K-step of
+// Weight gradient: wgrad_taprow.h's plan with K = the coarse voxels, a tile kDwTR coarse rows (flattened b, iz,
+// iy).  Wave kp runs the rows kp, kp + 4, ... of each tile (four partial sums of K, a slot each).  Per K-step of
 // four coarse voxels a wave issues two v_mfma_f32_16x16x4_f32: M = the 16 ci, N = 8 co x the taps (tx 0 | tx 1),
-// then N = 8 co x (tx 2 | unused).  Per tile the workgroup stages in LDS, once,
+// then N = 8 co x (tx 2 | unused).  Per tile the workgroup stages
 //   x:  channels-last: 16 voxel records of 16 floats per row (A read: lane (m, kq) at kq * 16 + m, 64 consecutive
 //       floats); NCDHW: 16 channel records of 18 floats per row (lane at m * 18 + kq: the 32 lanes of a half on
 //       32 banks);
 //   gy: the tap row's fine row (b, 2 iz - cz + tz, 2 iy - cy + ty) of each coarse row, per co the 34 fine voxels
 //       2 x0 - cx + j as a record of 36 floats (B read: lane (co, h, kq) at co * 36 + 2 kq + h: 32 banks per half).
-// Coarse rows whose fine row is off the box are skipped (their products are all 0).  Each wave stores its blocks
-// into its partial [27][16][8] slot -- every slot entry is written exactly once per launch by one of the nine tap
-// rows' workgroups, none relies on a zeroed workspace -- and deconv3d_wgrad_reduce_kernel sums the slots in slot
-// order (deterministic, no atomics).
+// Coarse rows whose fine row is off the box are skipped (their products are all 0).  The slot is [27][16][8]; a
+// tap's entries come from one of the nine tap rows' workgroups.
 #include "launchers.h"
-#include "packed.h"
+#include "wgrad_taprow.h"
 
 namespace mvs {
 namespace {
@@ -119,10 +115,9 @@ __global__ __launch_bounds__(kBlock) void deconv3d_dgrad_kernel(const float* __r
 // ---------------------------------------------------------------------------------------------------------
 // weight gradient
 // ---------------------------------------------------------------------------------------------------------
-constexpr int kDwTX = 16;                // coarse x-voxels of a tile
+constexpr int kDwTX = kTapRowTX;         // coarse x-voxels of a tile
 constexpr int kDwTR = 16;                // coarse rows of a tile
 constexpr int kDwKP = 4;                 // partial sums of K per workgroup: the waves split the tile's rows
-constexpr int kDwChunks = 168;           // K chunks: x 9 tap rows = 1512 workgroups
 constexpr int kDwFX = 2 * kDwTX + 2;     // staged fine voxels per (row, co)
 constexpr int kDwFS = 36;                // floats per staged gy record
 constexpr int kDwXS = 18;                // floats per staged x channel record (NCDHW)
@@ -137,8 +132,7 @@ struct DwGeo {
   int Iz, Iy, Ix;
   int Oz, Oy, Ox;
   int cz, cy, cx;
-  int rows;              // B * Iz * Iy coarse rows
-  int tiles_x, tiles;    // x tiles per row group, tiles in all
+  TapRowGeo t;           // rows: B * Iz * Iy coarse rows
 };
 
 template <bool XCL>
@@ -147,11 +141,9 @@ __global__ __launch_bounds__(kBlock) void deconv3d_wgrad_kernel(const float* __r
                                                                float* __restrict__ part, DwGeo g) {
   __shared__ __attribute__((aligned(16))) float cs[kDwTR * kDwXRow];
   __shared__ __attribute__((aligned(16))) float fs[kDwTR * kDCout * kDwFS];
-  __shared__ long long rowc[kDwTR], rowf[kDwTR];   // element offsets of the tile's rows (rowf -1: no such row)
   const int tid = (int)threadIdx.x, lane = tid & 63, kp = tid >> 6;
   const int m = lane & 15, kq = lane >> 4;
-  const int row_tap = (int)blockIdx.x % 9, chunk = (int)blockIdx.x / 9, chunks = (int)gridDim.x / 9;
-  const int tz = row_tap / 3, ty = row_tap % 3;
+  const TapRowBlock blk = taprow_block();
   const size_t plane = (size_t)g.Oz * g.Oy * g.Ox, ivol = (size_t)g.Iz * g.Iy * g.Ix;
   // A: lane (m, kq) supplies x[voxel 4 s + kq][ci = m]; B: lane (n = m, kq) supplies gy[co = n & 7][fine voxel
   // 2 (4 s + kq) + tx], tx = n >> 3 (first MFMA) or 2 (second; its columns 8-15 are not stored)
@@ -162,93 +154,76 @@ __global__ __launch_bounds__(kBlock) void deconv3d_wgrad_kernel(const float* __r
   acc[0] = f4v{0.0f, 0.0f, 0.0f, 0.0f};
   acc[1] = f4v{0.0f, 0.0f, 0.0f, 0.0f};
 
-  for (int tile = chunk; tile < g.tiles; tile += chunks) {   // workgroup-uniform
-    const int x0 = (tile % g.tiles_x) * kDwTX, row0 = (tile / g.tiles_x) * kDwTR;
-    const int fx0 = 2 * x0 - g.cx;   // the tile's first fine voxel along x (may be negative)
-    __syncthreads();   // the previous tile's operand reads are done
-    if (tid < kDwTR) {
-      const int R = row0 + tid;
-      long long oc = 0, of = -1;
-      if (R < g.rows) {
+  taprow_walk<kDwTR>(
+      blk, g.t,
+      [&](int R, long long& oc, long long& of) {
         const int iy = R % g.Iy, t = R / g.Iy;
         const int iz = t % g.Iz, b = t / g.Iz;
-        const int fz = 2 * iz - g.cz + tz, fy = 2 * iy - g.cy + ty;
+        const int fz = 2 * iz - g.cz + blk.tz, fy = 2 * iy - g.cy + blk.ty;
         // x[b][iz][iy][0][0] (channels-last) or x[b][0][iz][iy][0] (NCDHW)
         oc = XCL ? (long long)R * g.Ix * kDCin
                  : (long long)b * kDCin * (long long)ivol + ((long long)iz * g.Iy + iy) * g.Ix;
         if (fz >= 0 && fz < g.Oz && fy >= 0 && fy < g.Oy)
           of = (long long)b * kDCout * (long long)plane + ((long long)fz * g.Oy + fy) * g.Ox;   // gy[b][0][fz][fy][0]
-      }
-      rowc[tid] = oc;
-      rowf[tid] = of;
-    }
-    __syncthreads();
-    // stage x; voxels past the extent read 0 (their products vanish)
-    if constexpr (XCL) {   // items (row, voxel, 16-byte chunk), chunk fastest: coalesced channels-last loads
-      for (int e = tid; e < kDwTR * kDwTX * (kDCin / 4); e += kBlock) {
-        const int c4 = e % (kDCin / 4), v = e / (kDCin / 4);
-        const int r = v / kDwTX, xi = v % kDwTX;
-        if (rowf[r] < 0) continue;
-        f4v val{0.0f, 0.0f, 0.0f, 0.0f};
-        if (x0 + xi < g.Ix) val = *reinterpret_cast<const f4v*>(x + rowc[r] + (long long)(x0 + xi) * kDCin + 4 * c4);
-        *reinterpret_cast<f4v*>(cs + r * kDwXRow + xi * kDCin + 4 * c4) = val;
-      }
-    } else {               // items (row, channel, voxel), voxel fastest
-      for (int e = tid; e < kDwTR * kDCin * kDwTX; e += kBlock) {
-        const int xi = e % kDwTX, t = e / kDwTX;
-        const int ci = t % kDCin, r = t / kDCin;
-        if (rowf[r] < 0) continue;
-        float val = 0.0f;
-        if (x0 + xi < g.Ix) val = x[rowc[r] + (long long)ci * (long long)ivol + (x0 + xi)];
-        cs[r * kDwXRow + ci * kDwXS + xi] = val;
-      }
-    }
-    // stage gy: items (row, co, fine voxel j), j fastest; voxels off the row read 0
-    for (int e = tid; e < kDwTR * kDCout * kDwFX; e += kBlock) {
-      const int j = e % kDwFX, t = e / kDwFX;
-      const int co = t % kDCout, r = t / kDCout;
-      const long long o = rowf[r];
-      if (o < 0) continue;
-      const int fx = fx0 + j;
-      float val = 0.0f;
-      if (fx >= 0 && fx < g.Ox) val = gy[o + (long long)co * (long long)plane + fx];
-      fs[(r * kDCout + co) * kDwFS + j] = val;
-    }
-    __syncthreads();
-    // the K-steps of the staged tile
+      },
+      [&](int x0, const long long* rowc, const long long* rowf) {
+        const int fx0 = 2 * x0 - g.cx;   // the tile's first fine voxel along x (may be negative)
+        // stage x; voxels past the extent read 0 (their products vanish)
+        if constexpr (XCL) {   // items (row, voxel, 16-byte chunk), chunk fastest: coalesced channels-last loads
+          for (int e = tid; e < kDwTR * kDwTX * (kDCin / 4); e += kBlock) {
+            const int c4 = e % (kDCin / 4), v = e / (kDCin / 4);
+            const int r = v / kDwTX, xi = v % kDwTX;
+            if (rowf[r] < 0) continue;
+            f4v val{0.0f, 0.0f, 0.0f, 0.0f};
+            if (x0 + xi < g.Ix)
+              val = *reinterpret_cast<const f4v*>(x + rowc[r] + (long long)(x0 + xi) * kDCin + 4 * c4);
+            *reinterpret_cast<f4v*>(cs + r * kDwXRow + xi * kDCin + 4 * c4) = val;
+          }
+        } else {               // items (row, channel, voxel), voxel fastest
+          for (int e = tid; e < kDwTR * kDCin * kDwTX; e += kBlock) {
+            const int xi = e % kDwTX, t = e / kDwTX;
+            const int ci = t % kDCin, r = t / kDCin;
+            if (rowf[r] < 0) continue;
+            float val = 0.0f;
+            if (x0 + xi < g.Ix) val = x[rowc[r] + (long long)ci * (long long)ivol + (x0 + xi)];
+            cs[r * kDwXRow + ci * kDwXS + xi] = val;
+          }
+        }
+        // stage gy: items (row, co, fine voxel j), j fastest; voxels off the row read 0
+        for (int e = tid; e < kDwTR * kDCout * kDwFX; e += kBlock) {
+          const int j = e % kDwFX, t = e / kDwFX;
+          const int co = t % kDCout, r = t / kDCout;
+          const long long o = rowf[r];
+          if (o < 0) continue;
+          const int fx = fx0 + j;
+          float val = 0.0f;
+          if (fx >= 0 && fx < g.Ox) val = gy[o + (long long)co * (long long)plane + fx];
+          fs[(r * kDCout + co) * kDwFS + j] = val;
+        }
+        __syncthreads();
+        // the K-steps of the staged tile
 #pragma unroll 1
-    for (int r = kp; r < kDwTR; r += kDwKP) {
-      if (rowf[r] < 0) continue;   // wave-uniform: no such row, or its fine row is off the box
-      const float* ar = cs + r * kDwXRow + aoff;
-      const float* br = fs + r * kDCout * kDwFS;
+        for (int r = kp; r < kDwTR; r += kDwKP) {
+          if (rowf[r] < 0) continue;   // wave-uniform: no such row, or its fine row is off the box
+          const float* ar = cs + r * kDwXRow + aoff;
+          const float* br = fs + r * kDCout * kDwFS;
 #pragma unroll
-      for (int s = 0; s < kDwTX / 4; ++s) {
-        const float a = ar[s * astep];
-        const float b0 = br[boff0 + 8 * s], b1 = br[boff1 + 8 * s];
-        acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b0, acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b1, acc[1], 0, 0, 0);
-      }
-    }
-  }
+          for (int s = 0; s < kDwTX / 4; ++s) {
+            const float a = ar[s * astep];
+            const float b0 = br[boff0 + 8 * s], b1 = br[boff1 + 8 * s];
+            acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b0, acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b1, acc[1], 0, 0, 0);
+          }
+        }
+      });
   // partial slot [27][ci][co]: acc[q][i] = D[ci = 4 kq + i][n = m]: tap tx = n >> 3 (q = 0) or 2 (q = 1, n < 8)
-  float* slot = part + ((size_t)chunk * kDwKP + kp) * kDwSlot;
+  float* slot = part + ((size_t)blk.chunk * kDwKP + kp) * kDwSlot;
   const int co = m & 7;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    slot[((row_tap * 3 + (m >> 3)) * kDCin + 4 * kq + i) * kDCout + co] = acc[0][i];
-    if (m < 8) slot[((row_tap * 3 + 2) * kDCin + 4 * kq + i) * kDCout + co] = acc[1][i];
+    slot[((blk.row_tap * 3 + (m >> 3)) * kDCin + 4 * kq + i) * kDCout + co] = acc[0][i];
+    if (m < 8) slot[((blk.row_tap * 3 + 2) * kDCin + 4 * kq + i) * kDCout + co] = acc[1][i];
   }
-}
-
-// dW[ci][co][t] = the slots' [t][ci][co] entries summed in slot order (fixed: deterministic)
-__global__ __launch_bounds__(kBlock) void deconv3d_wgrad_reduce_kernel(const float* __restrict__ part, int slots,
-                                                                      float* __restrict__ dw) {
-  const int i = (int)(blockIdx.x * kBlock + threadIdx.x);   // (t, ci, co): consecutive lanes, consecutive co
-  if (i >= kDwSlot) return;
-  float s = 0.0f;
-  for (int k = 0; k < slots; ++k) s += part[(size_t)k * kDwSlot + i];
-  const int co = i % kDCout, ci = (i / kDCout) % kDCin, t = i / (kDCout * kDCin);
-  dw[((size_t)ci * kDCout + co) * 27 + t] = s;
 }
 
 DwGeo dw_geo(int B, const int* in, const int* crop, const int* out) {
@@ -257,30 +232,24 @@ DwGeo dw_geo(int B, const int* in, const int* crop, const int* out) {
   g.Iz = in[0], g.Iy = in[1], g.Ix = in[2];
   g.Oz = out[0], g.Oy = out[1], g.Ox = out[2];
   g.cz = crop ? crop[0] : 0, g.cy = crop ? crop[1] : 0, g.cx = crop ? crop[2] : 0;
-  g.rows = B * g.Iz * g.Iy;
-  g.tiles_x = (g.Ix + kDwTX - 1) / kDwTX;
-  g.tiles = g.tiles_x * ((g.rows + kDwTR - 1) / kDwTR);
+  g.t = taprow_geo(B * g.Iz * g.Iy, g.Ix, kDwTR);
   return g;
 }
-
-inline int dw_chunks(const DwGeo& g) { return g.tiles < kDwChunks ? g.tiles : kDwChunks; }
 
 }  // namespace
 
 size_t deconv3d_wgrad_workspace_bytes(int B, const int* in, const int* out) {
-  return (size_t)dw_chunks(dw_geo(B, in, nullptr, out)) * kDwKP * kDwSlot * sizeof(float);
+  return taprow_workspace_bytes(dw_geo(B, in, nullptr, out).t, kDwKP, kDwSlot);
 }
 
 void launch_deconv3d_wgrad(const float* x, bool x_cl, const float* gy, int B, const int* in, const int* crop,
                            const int* out, float* part, float* dw, hipStream_t s) {
   const DwGeo g = dw_geo(B, in, crop, out);
-  const int chunks = dw_chunks(g);
   if (x_cl)
-    hipLaunchKernelGGL((deconv3d_wgrad_kernel<true>), dim3(9u * (unsigned)chunks), dim3(kBlock), 0, s, x, gy, part, g);
+    hipLaunchKernelGGL((deconv3d_wgrad_kernel<true>), taprow_grid(g.t), dim3(kBlock), 0, s, x, gy, part, g);
   else
-    hipLaunchKernelGGL((deconv3d_wgrad_kernel<false>), dim3(9u * (unsigned)chunks), dim3(kBlock), 0, s, x, gy, part, g);
-  hipLaunchKernelGGL(deconv3d_wgrad_reduce_kernel, dim3((kDwSlot + kBlock - 1) / kBlock), dim3(kBlock), 0, s, part,
-                     chunks * kDwKP, dw);
+    hipLaunchKernelGGL((deconv3d_wgrad_kernel<false>), taprow_grid(g.t), dim3(kBlock), 0, s, x, gy, part, g);
+  launch_wgrad_reduce(part, taprow_chunks(g.t) * kDwKP, kDCin, kDCout, dw, s);
 }
 
 void launch_deconv3d_dgrad(const float* gy, const float* w27, float* gx, bool x_cl, int B, const int* in,

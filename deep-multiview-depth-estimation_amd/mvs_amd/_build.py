@@ -24,7 +24,8 @@ HEADERS = [os.path.join(REPO_ROOT, "include", "mvs_cost_volume.h"),
            os.path.join(REPO_ROOT, "include", "train", "mvs_region_train.h"),
            os.path.join(CSRC, "common.h"), os.path.join(CSRC, "launchers.h"),
            os.path.join(CSRC, "packed.h"), os.path.join(CSRC, "region_conv.h"),
-           os.path.join(CSRC, "sampling_matrix.h"), os.path.join(CSRC, "split.h")]
+           os.path.join(CSRC, "sampling_matrix.h"), os.path.join(CSRC, "split.h"),
+           os.path.join(CSRC, "wgrad_taprow.h")]
 # per-source device flags, compiled as a separate object: the fused head (cv_head.hip) without packed
 # fp32 VALU instructions -- with v_pk_{fma,add,mul}_f32 in its gather / variance code, the .z / .w halves of
 # a producer item's variance came out wrong in a schedule-dependent share of launches (0 to 100 % of

@@ -743,6 +743,31 @@ def conv3d_k3_wgrad(x: torch.Tensor, gy: torch.Tensor) -> torch.Tensor:
 REGION_WGRAD_CHANNELS = (16, 32, 64)   # c_in = c_out of mvs_conv3d_region_wgrad
 
 
+def _wgrad_launch(name, nbytes, geometry_error, dw_shape, device, *args):
+    """The weight-gradient wrappers' tail: the workspace of nbytes (0: the entry point's geometry check refused,
+    ValueError(geometry_error)) and dw, then lib.<name>(*args, dw, workspace, stream), checked."""
+    if nbytes == 0:
+        raise ValueError(geometry_error)
+    ws = torch.empty(nbytes // 4, device=device, dtype=_F32)
+    dw = torch.empty(dw_shape, device=device, dtype=_F32)
+    st = getattr(_lib.load(), name)(*args, _lib.ptr(dw), _lib.ptr(ws), _lib.stream_handle(device))
+    _lib.check(st, name)
+    return dw
+
+
+def _dgrad_geometry(name, in_size, offset, out_shape, workspace_bytes, geometry_error):
+    """The input-gradient wrappers' validation of in_size (argument `name`) and pad_lo / crop, then the geometry
+    check they share with their weight gradient (workspace_bytes(size, out) == 0: refused); returns the three as
+    C int arrays (size, offset, out)."""
+    if len(in_size) != 3 or min(in_size) < 1:
+        raise ValueError("%s: three ints >= 1 expected, got %s" % (name, in_size))
+    off = _ints3(_pad3(offset))
+    size, out = _ints3(in_size), _ints3(out_shape)
+    if workspace_bytes(size, out) == 0:
+        raise ValueError(geometry_error % (in_size, tuple(out_shape)))
+    return size, off, out
+
+
 def conv3d_region_wgrad(x_cl: torch.Tensor, gy_cl: torch.Tensor) -> torch.Tensor:
     """Weight gradient of a stride-1 region convolution nn.Conv3d(C, C, 3, padding=0, bias=False)
     (model.py:108-113 conv_k_1 on the padded crop) from its channels-last input x_cl [B, Lz, Ly, Lx, C] and
@@ -759,18 +784,14 @@ def conv3d_region_wgrad(x_cl: torch.Tensor, gy_cl: torch.Tensor) -> torch.Tensor
     x_cl = x_cl.to(_F32).contiguous()
     gy_cl = gy_cl.to(device=x_cl.device, dtype=_F32).contiguous()
     size = _ints3(x_cl.shape[1:4])
-    nbytes = lib.mvs_conv3d_region_wgrad_workspace_bytes(b, c, size)
-    if nbytes == 0:
-        raise ValueError("crop %s: every extent >= 3 and B * Lz * Ly * Lx < 2^31 expected" % (tuple(x_cl.shape[1:4]),))
-    ws = torch.empty(nbytes // 4, device=x_cl.device, dtype=_F32)
-    dw = torch.empty((c, c, 3, 3, 3), device=x_cl.device, dtype=_F32)
-    st = lib.mvs_conv3d_region_wgrad(_lib.ptr(x_cl), _lib.ptr(gy_cl), b, c, size, _lib.ptr(dw), _lib.ptr(ws),
-                                     _lib.stream_handle(x_cl.device))
-    _lib.check(st, "mvs_conv3d_region_wgrad")
-    return dw
+    return _wgrad_launch("mvs_conv3d_region_wgrad", lib.mvs_conv3d_region_wgrad_workspace_bytes(b, c, size),
+                         "crop %s: every extent >= 3 and B * Lz * Ly * Lx < 2^31 expected" % (tuple(x_cl.shape[1:4]),),
+                         (c, c, 3, 3, 3), x_cl.device, _lib.ptr(x_cl), _lib.ptr(gy_cl), b, c, size)
 
 
 S2_BWD_CHANNELS = (32, 112)   # (c_in, c_out) of mvs_conv3d_s2_region_wgrad / _dgrad: conv_1_0 | conv_2_0 | conv_3_0
+_S2_GEOMETRY = "volume %s, box %s: every extent >= 1 and B * voxels < 2^31 expected"
+_T2_GEOMETRY = "input %s, box %s: every extent >= 1, B * voxels < 2^31 and a sample of gy < 4 GB expected"
 
 
 def _pad3(pad_lo):
@@ -799,16 +820,9 @@ def conv3d_s2_region_wgrad(x: torch.Tensor, gy_cl: torch.Tensor, pad_lo) -> torc
     x = x.to(_F32).contiguous()
     gy_cl = gy_cl.to(device=x.device, dtype=_F32).contiguous()
     dims, out = _ints3(x.shape[2:]), _ints3(gy_cl.shape[1:4])
-    nbytes = lib.mvs_conv3d_s2_region_wgrad_workspace_bytes(b, dims, out)
-    if nbytes == 0:
-        raise ValueError("volume %s, box %s: every extent >= 1 and B * voxels < 2^31 expected"
-                         % (tuple(x.shape[2:]), tuple(gy_cl.shape[1:4])))
-    ws = torch.empty(nbytes // 4, device=x.device, dtype=_F32)
-    dw = torch.empty((cout, cin, 3, 3, 3), device=x.device, dtype=_F32)
-    st = lib.mvs_conv3d_s2_region_wgrad(_lib.ptr(x), _lib.ptr(gy_cl), b, dims, pad, out, _lib.ptr(dw), _lib.ptr(ws),
-                                        _lib.stream_handle(x.device))
-    _lib.check(st, "mvs_conv3d_s2_region_wgrad")
-    return dw
+    return _wgrad_launch("mvs_conv3d_s2_region_wgrad", lib.mvs_conv3d_s2_region_wgrad_workspace_bytes(b, dims, out),
+                         _S2_GEOMETRY % (tuple(x.shape[2:]), tuple(gy_cl.shape[1:4])), (cout, cin, 3, 3, 3), x.device,
+                         _lib.ptr(x), _lib.ptr(gy_cl), b, dims, pad, out)
 
 
 def conv3d_s2_region_dgrad(gy_cl: torch.Tensor, w: torch.Tensor, dims, pad_lo) -> torch.Tensor:
@@ -824,16 +838,12 @@ def conv3d_s2_region_dgrad(gy_cl: torch.Tensor, w: torch.Tensor, dims, pad_lo) -
     if gy_cl.dim() != 5 or gy_cl.shape[4] != cout or tuple(w.shape) != (cout, cin, 3, 3, 3):
         raise ValueError("gy_cl [B, Oz, Oy, Ox, %d] and w [%d, %d, 3, 3, 3] expected, got %s and %s"
                          % (cout, cout, cin, tuple(gy_cl.shape), tuple(w.shape)))
-    if len(dims) != 3 or min(dims) < 1:
-        raise ValueError("dims: three ints >= 1 expected, got %s" % (dims,))
-    pad = _ints3(_pad3(pad_lo))
     b = gy_cl.shape[0]
+    size, pad, out = _dgrad_geometry(
+        "dims", dims, pad_lo, gy_cl.shape[1:4],
+        lambda size, out: lib.mvs_conv3d_s2_region_wgrad_workspace_bytes(b, size, out), _S2_GEOMETRY)
     gy_cl = gy_cl.to(_F32).contiguous()
     w27 = w.detach().to(device=gy_cl.device, dtype=_F32).permute(2, 3, 4, 1, 0).reshape(27, cin, cout).contiguous()
-    size, out = _ints3(dims), _ints3(gy_cl.shape[1:4])
-    if lib.mvs_conv3d_s2_region_wgrad_workspace_bytes(b, size, out) == 0:   # (the two share their geometry check)
-        raise ValueError("volume %s, box %s: every extent >= 1 and B * voxels < 2^31 expected"
-                         % (dims, tuple(gy_cl.shape[1:4])))
     gx = torch.empty((b, cin) + dims, device=gy_cl.device, dtype=_F32)
     st = lib.mvs_conv3d_s2_region_dgrad(_lib.ptr(gy_cl), _lib.ptr(w27), b, size, pad, out, _lib.ptr(gx),
                                         _lib.stream_handle(gy_cl.device))
@@ -869,16 +879,10 @@ def conv3d_t2_region_wgrad(x: torch.Tensor, gy: torch.Tensor, crop) -> torch.Ten
     x_cl = _cl5(x)
     gy_cl = _cl5(gy.to(x.device))
     size, out = _ints3(x_cl.shape[1:4]), _ints3(gy_cl.shape[1:4])
-    nbytes = lib.mvs_conv3d_t2_region_wgrad_workspace_bytes(b, cin, cout, size, out)
-    if nbytes == 0:
-        raise ValueError("input %s, box %s: every extent >= 1, B * voxels < 2^31 and a sample of gy < 4 GB expected"
-                         % (tuple(x_cl.shape[1:4]), tuple(gy_cl.shape[1:4])))
-    ws = torch.empty(nbytes // 4, device=x.device, dtype=_F32)
-    dw = torch.empty((cin, cout, 3, 3, 3), device=x.device, dtype=_F32)
-    st = lib.mvs_conv3d_t2_region_wgrad(_lib.ptr(x_cl), _lib.ptr(gy_cl), b, cin, cout, size, cr, out, _lib.ptr(dw),
-                                        _lib.ptr(ws), _lib.stream_handle(x.device))
-    _lib.check(st, "mvs_conv3d_t2_region_wgrad")
-    return dw
+    return _wgrad_launch("mvs_conv3d_t2_region_wgrad",
+                         lib.mvs_conv3d_t2_region_wgrad_workspace_bytes(b, cin, cout, size, out),
+                         _T2_GEOMETRY % (tuple(x_cl.shape[1:4]), tuple(gy_cl.shape[1:4])), (cin, cout, 3, 3, 3),
+                         x.device, _lib.ptr(x_cl), _lib.ptr(gy_cl), b, cin, cout, size, cr, out)
 
 
 def conv3d_t2_region_dgrad(gy: torch.Tensor, w: torch.Tensor, in_size, crop) -> torch.Tensor:
@@ -894,16 +898,12 @@ def conv3d_t2_region_dgrad(gy: torch.Tensor, w: torch.Tensor, in_size, crop) -> 
             or gy.shape[1] != w.shape[1] or tuple(w.shape[2:]) != (3, 3, 3)):
         raise ValueError("gy [B, c_out, Oz, Oy, Ox] and w [c_in, c_out, 3, 3, 3] with (c_in, c_out) in %s expected, "
                          "got %s and %s" % (T2_BWD_CHANNELS, tuple(gy.shape), tuple(w.shape)))
-    if len(in_size) != 3 or min(in_size) < 1:
-        raise ValueError("in_size: three ints >= 1 expected, got %s" % (in_size,))
-    cr = _ints3(_pad3(crop))
     b, cin, cout = gy.shape[0], w.shape[0], w.shape[1]
+    size, cr, out = _dgrad_geometry(
+        "in_size", in_size, crop, gy.shape[2:],
+        lambda size, out: lib.mvs_conv3d_t2_region_wgrad_workspace_bytes(b, cin, cout, size, out), _T2_GEOMETRY)
     gy_cl = _cl5(gy)
     w27 = w.detach().to(device=gy.device, dtype=_F32).permute(2, 3, 4, 0, 1).reshape(27, cin, cout).contiguous()
-    size, out = _ints3(in_size), _ints3(gy_cl.shape[1:4])
-    if lib.mvs_conv3d_t2_region_wgrad_workspace_bytes(b, cin, cout, size, out) == 0:   # (one geometry check for both)
-        raise ValueError("input %s, box %s: every extent >= 1, B * voxels < 2^31 and a sample of gy < 4 GB expected"
-                         % (in_size, tuple(gy_cl.shape[1:4])))
     gx = torch.empty((b,) + in_size + (cin,), device=gy.device, dtype=_F32)
     st = lib.mvs_conv3d_t2_region_dgrad(_lib.ptr(gy_cl), _lib.ptr(w27), b, cin, cout, size, cr, out, _lib.ptr(gx),
                                         _lib.stream_handle(gy.device))
@@ -947,16 +947,9 @@ def deconv3d_k3s2_wgrad(x: torch.Tensor, gy: torch.Tensor, crop) -> torch.Tensor
     xm, flags = _x_layout(x)
     gy = gy.to(device=x.device, dtype=_F32).contiguous()
     size, out = _ints3(x.shape[2:]), _ints3(gy.shape[2:])
-    nbytes = lib.mvs_deconv3d_k3s2_wgrad_workspace_bytes(b, cin, cout, size, out)
-    if nbytes == 0:
-        raise ValueError("input %s, box %s: every extent >= 1, B * voxels < 2^31 and a sample of gy < 4 GB expected"
-                         % (tuple(x.shape[2:]), tuple(gy.shape[2:])))
-    ws = torch.empty(nbytes // 4, device=x.device, dtype=_F32)
-    dw = torch.empty((cin, cout, 3, 3, 3), device=x.device, dtype=_F32)
-    st = lib.mvs_deconv3d_k3s2_wgrad(_lib.ptr(xm), flags, _lib.ptr(gy), b, cin, cout, size, cr, out, _lib.ptr(dw),
-                                     _lib.ptr(ws), _lib.stream_handle(x.device))
-    _lib.check(st, "mvs_deconv3d_k3s2_wgrad")
-    return dw
+    return _wgrad_launch("mvs_deconv3d_k3s2_wgrad", lib.mvs_deconv3d_k3s2_wgrad_workspace_bytes(b, cin, cout, size, out),
+                         _T2_GEOMETRY % (tuple(x.shape[2:]), tuple(gy.shape[2:])), (cin, cout, 3, 3, 3), x.device,
+                         _lib.ptr(xm), flags, _lib.ptr(gy), b, cin, cout, size, cr, out)
 
 
 def deconv3d_k3s2_dgrad(gy: torch.Tensor, w: torch.Tensor, in_size, crop, channels_last: bool = False) -> torch.Tensor:
@@ -973,16 +966,12 @@ def deconv3d_k3s2_dgrad(gy: torch.Tensor, w: torch.Tensor, in_size, crop, channe
     if gy.dim() != 5 or gy.shape[1] != cout or tuple(w.shape) != (cin, cout, 3, 3, 3):
         raise ValueError("gy [B, %d, Oz, Oy, Ox] and w [%d, %d, 3, 3, 3] expected, got %s and %s"
                          % (cout, cin, cout, tuple(gy.shape), tuple(w.shape)))
-    if len(in_size) != 3 or min(in_size) < 1:
-        raise ValueError("in_size: three ints >= 1 expected, got %s" % (in_size,))
-    cr = _ints3(_pad3(crop))
     b = gy.shape[0]
+    size, cr, out = _dgrad_geometry(
+        "in_size", in_size, crop, gy.shape[2:],
+        lambda size, out: lib.mvs_deconv3d_k3s2_wgrad_workspace_bytes(b, cin, cout, size, out), _T2_GEOMETRY)
     gy = gy.to(_F32).contiguous()
     w27 = w.detach().to(device=gy.device, dtype=_F32).permute(2, 3, 4, 0, 1).reshape(27, cin, cout).contiguous()
-    size, out = _ints3(in_size), _ints3(gy.shape[2:])
-    if lib.mvs_deconv3d_k3s2_wgrad_workspace_bytes(b, cin, cout, size, out) == 0:   # (one geometry check for both)
-        raise ValueError("input %s, box %s: every extent >= 1, B * voxels < 2^31 and a sample of gy < 4 GB expected"
-                         % (in_size, tuple(gy.shape[2:])))
     flags = _lib.MVS_LAYOUT_CHANNELS_LAST if channels_last else 0
     gx = torch.empty((b,) + in_size + (cin,) if channels_last else (b, cin) + in_size, device=gy.device, dtype=_F32)
     st = lib.mvs_deconv3d_k3s2_dgrad(_lib.ptr(gy), _lib.ptr(w27), flags, b, cin, cout, size, cr, out, _lib.ptr(gx),

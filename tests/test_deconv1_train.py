@@ -6,8 +6,8 @@ the workspace held, three and more passes of its persistent tile loop, element o
 autograd routing, the default path unchanged, and the regulariser's whole chain.
 
 The constants below MIRROR csrc/deconv3d_region_bwd.hip (the library does not export them):
-  168   kDwChunks, persistent workgroups (K chunks) per tap row
-  16    kDwTX, coarse x-voxels of a tile
+  168   kTapRowChunks (csrc/wgrad_taprow.h), persistent workgroups (K chunks) per tap row
+  16    kDwTX = kTapRowTX, coarse x-voxels of a tile
   16    kDwTR, coarse rows (flattened b, iz, iy) of a tile
   4     kDwKP, partial slots per chunk (the four waves split the tile's rows)
   tiles = ceil(Ix / 16) * ceil(B * Iz * Iy / 16);  workspace = min(tiles, 168) * 4 slots of [27][16][8]

@@ -10,12 +10,12 @@ passes, most of them three or more, with a ragged last pass (tiles % 168 != 0), 
 their one nonzero product in a chosen pass.
 
 The constants below MIRROR the kernels' (they are not imported: the library does not export them):
-  168        kRwChunks (conv3d_region_wgrad.hip) = kSwChunks (conv3d_s2_wgrad.hip), workgroups per tap row
-  16         kRwTX = kSwTX, output x-voxels of a tile
+  168        kTapRowChunks (wgrad_taprow.h, the plan both kernels share), workgroups per tap row
+  16         kTapRowTX, output x-voxels of a tile
   28/10/6    RwTile<C>::TR, output rows (flattened b, z, y) of a stride-1 tile for C = 16 / 32 / 64
   4/1/1      RwTile<C>::KP, partial slots per workgroup (C = 16: the four waves split the rows)
   5          kSwTR, output rows of a stride-2 tile
-  tiles = ceil(Ox / 16) * ceil(B * Oz * Oy / TR)          rw_geo / sw_geo
+  tiles = ceil(Ox / 16) * ceil(B * Oz * Oy / TR)          taprow_geo
 Every case first asserts, through _s1_plan / _s2_plan, that its tile count reaches the passes it is there for
 and that the library's workspace size is exactly the capped one (168 slots): a change of the chunk count fails
 that assertion, and no case passes while running a single pass.  (A change of TR alone moves the tile counts

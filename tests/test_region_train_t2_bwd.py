@@ -6,8 +6,8 @@ whatever the workspace held, three and more passes of its persistent tile loop, 
 the autograd routing, the default path unchanged, and the regulariser's whole chain.
 
 The constants below MIRROR csrc/conv3d_t2_wgrad.hip (the library does not export them):
-  168      kTwChunks, persistent workgroups (K chunks) per tap row
-  16       kTwTX, coarse x-voxels of a tile
+  168      kTapRowChunks (csrc/wgrad_taprow.h), persistent workgroups (K chunks) per tap row
+  16       kTapRowTX, coarse x-voxels of a tile
   6 / 12   TwTile::TR, coarse rows (flattened b, iz, iy) of a tile for (64, 32) / (32, 16)
   1 / 4    TwTile::KP, partial slots per chunk ((32, 16): the four waves split the tile's rows)
   tiles = ceil(Ix / 16) * ceil(B * Iz * Iy / TR);  workspace = min(tiles, 168) * KP slots of [27][c_in][c_out]
