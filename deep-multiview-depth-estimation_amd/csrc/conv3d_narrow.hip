@@ -58,12 +58,10 @@ struct Head1 {
 };
 
 // C1's waves per SIMD: 3 keeps conv_0_0's occupancy (168 registers; a few spill outside the pass loop)
-#ifndef MVS_HEAD_WAVES
-#define MVS_HEAD_WAVES 3
-#endif
+constexpr int kHeadWaves = 3;
 
 template <int COUT, int C4, bool WZ = false, int DT = kDT, bool FOLD = false, bool C1 = false>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(C1 ? MVS_HEAD_WAVES : 1)))
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(C1 ? kHeadWaves : 1)))
 void conv3d_k3_narrow_kernel(
     const float* __restrict__ in, const float* __restrict__ wt, float* __restrict__ out, int Cin,
     int D, int H, int W, int tiles_x, int tiles_y, int dgroups, int n_batch, const float* __restrict__ bn_scale,
@@ -336,10 +334,7 @@ void conv3d_k3_narrow_kernel(
 
 // COUT = 1 (conv_out): kOutDT output depths per thread -- the (DT + 2)-plane halo is re-read
 // (DT + 2) / DT times (cfg 2: 4 -> 1.5x, 8 -> 1.25x of the 503 MB input)
-#ifndef MVS_CONV_OUT_DT
-#define MVS_CONV_OUT_DT 8
-#endif
-constexpr int kOutDT = MVS_CONV_OUT_DT;
+constexpr int kOutDT = 8;
 
 template <int COUT, int C4, bool WZ = false, bool FOLD = false, bool C1 = false>
 void launch_narrow(const float* in, const float* weight, float* out, int B, int Cin, int D, int H, int W,

@@ -55,14 +55,6 @@ struct GeoS {
 // (CostVolumeReg.forward_live_train): one launch with their 16 + 32 + 64 output channels loads each
 // A fragment once for all seven column blocks (three launches loaded it three times)
 constexpr int kS2Multi = 112;
-#ifndef MVS_S2M_BLDS
-#define MVS_S2M_BLDS 1
-#endif
-// S1 64 -> 64 with the K block's weights in LDS, 2 row blocks per wave (3 waves per SIMD): train-mode
-// step 12.3 -> 12.1 ms (with 4 row blocks 274 registers, one wave per SIMD: 13.4 ms)
-#ifndef MVS_S1_BLDS
-#define MVS_S1_BLDS 1
-#endif
 
 // per-workgroup channel sums: the wave's per-lane partial sums s / q (channel nb * 16 + (lane & 15) of
 // column block nb) reduced over the lanes of equal channel, then over the waves in a fixed order, and
@@ -133,7 +125,7 @@ __global__ __launch_bounds__(kBlock) void conv3d_region_split_kernel(
   const int row0 = (bx * (kBlock / 64) + ((int)threadIdx.x >> 6)) * kRows;
   // wave-uniform; no barriers in this kernel unless sums are gathered (then every wave stays, the
   // ones past the rows on zeros)
-  if (row0 >= rows && !g.stats && !(MODE == kS2 && CO == kS2Multi) && !(MODE == kS1 && CI == 64 && MVS_S1_BLDS)) return;
+  if (row0 >= rows && !g.stats && !(MODE == kS2 && CO == kS2Multi) && !(MODE == kS1 && CI == 64)) return;
 
   // the input's scale: max|x| (+ max|x2|) 2^ex < 2^14; S2: the split volume's own exponent
   int ex;
@@ -213,7 +205,9 @@ __global__ __launch_bounds__(kBlock) void conv3d_region_split_kernel(
   // each K block's fragments are fetched once per workgroup into an LDS double buffer (one barrier per
   // K block; the next block's global loads in flight under this block's MFMAs) instead of by every wave
   // from L2.  Every wave runs the same K sequence (taps, then channel blocks).
-  constexpr bool BL = (MODE == kS2 && CO == kS2Multi && MVS_S2M_BLDS) || (MODE == kS1 && CI == 64 && MVS_S1_BLDS);
+  // S1 64 -> 64 the same way, 2 row blocks per wave (3 waves per SIMD): train-mode step 12.3 -> 12.1 ms
+  // (with 4 row blocks 274 registers, one wave per SIMD: 13.4 ms)
+  constexpr bool BL = (MODE == kS2 && CO == kS2Multi) || (MODE == kS1 && CI == 64);
   constexpr int BFR = NB * 2 * 64;                        // h8v per K block
   constexpr int BPER = (BFR + kBlock - 1) / kBlock;
   __shared__ h8v blds[BL ? 2 : 1][BL ? BFR : 1];
@@ -583,13 +577,11 @@ void launch_s1_lds(const float* x, const void* wf, int w_exp, float* y, const fl
 // channel blocks): bit-equal outputs.
 // (the K block's weight fragments staged in LDS once per workgroup, as the 3-in-1 S2 does: train-mode
 // step 12.0 -> 12.4 ms -- a barrier per K block of a class with 1-8 taps; dropped)
-// MVS_T2_TYB: class rows along y per tile / 4 (2: a 32 x 16 x 4 tile, 4 row blocks per wave, one
+// kT2TYB: class rows along y per tile / 4 (2: a 32 x 16 x 4 tile, 4 row blocks per wave, one
 // workgroup per CU: train-mode step 14.1 -> 15.5 ms; the LDS kernel on eval's small regions: eval step
 // 3.95 -> 4.24 ms, hence kT2LdsMinVoxels)
-#ifndef MVS_T2_TYB
-#define MVS_T2_TYB 1
-#endif
-template <int CI, int TXB, int TYB = MVS_T2_TYB>
+constexpr int kT2TYB = 1;
+template <int CI, int TXB, int TYB = kT2TYB>
 struct T2Tile : SplitRec<CI> {
   static constexpr int TX = 32 * TXB, TY = 8 * TYB, TZ = 4;
   static constexpr int PX = TX / 2 + 1, PY = TY / 2 + 1, PZ = TZ / 2 + 1, PV = PX * PY * PZ;
@@ -603,8 +595,8 @@ __global__ __launch_bounds__(kBlock) void conv3d_t2_split_lds_kernel(
     const float* __restrict__ bn_mean, GeoS g, int tiles_x, int tiles_y, int tiles_z, const uint32_t* __restrict__ xb,
     const uint32_t* __restrict__ xb2, uint32_t* __restrict__ yb) {
   using T = T2Tile<CI, TXB>;
-  constexpr int NB = CO / 16, CB = CI / 32, RB = 2 * TXB * MVS_T2_TYB;
-  constexpr int NYC = 4 * MVS_T2_TYB;   // class rows along y
+  constexpr int NB = CO / 16, CB = CI / 32, RB = 2 * TXB * kT2TYB;
+  constexpr int NYC = 4 * kT2TYB;   // class rows along y
   static_assert(CI % 32 == 0 && CO % 16 == 0, "channel counts");
   __shared__ __attribute__((aligned(16))) char lds[T::LDS];
 
@@ -850,12 +842,10 @@ int conv3d_region_split_kblocks(int c_in) { return c_in == 16 ? 14 : 27 * (c_in 
 // (0.11 -> 0.13 / 2.41 -> 2.81 ms: its 110 KB tile allows one workgroup per CU).  An LDS-staged
 // transposed kernel (one 17 x 5 x (TZ + 1) block per parity-class tile) measured no gain (0.31 ->
 // 0.34 ms): a class reads each input voxel through 1-8 taps only.
-#ifndef MVS_S1_LDS
-#define MVS_S1_LDS 3
-#endif
+constexpr int kS1Lds = 3;
 static bool split_uses_lds(int mode, int CI, int CO, bool per_lane, bool has_x2) {
   const int ci_bit = CI == 16 ? 1 : (CI == 32 ? 2 : (CI == 64 ? 4 : 0));
-  return (MVS_S1_LDS & ci_bit) && !per_lane && mode == kS1 && CI == CO && !has_x2;
+  return (kS1Lds & ci_bit) && !per_lane && mode == kS1 && CI == CO && !has_x2;
 }
 
 // row blocks per wave of the per-lane kernel: 4 for the stride-1 convs (each weight fragment feeds 4 row
@@ -864,17 +854,14 @@ static bool split_uses_lds(int mode, int CI, int CO, bool per_lane, bool has_x2)
 // The stride-1 kernel without LDS weights drops to 2 row blocks when 4 would leave fewer than kS1WideWgs
 // workgroups: eval's deep-level regions are small (conv_3_1 at cfg 2: 3.97 -> 3.87 ms per eval step with
 // 2), train mode's are large (4 measured best there: 15.3 against 15.5 ms per train-mode step).  With its
-// weights in LDS (64 channels, MVS_S1_BLDS) it always takes 2.  S2 with 1 / 4 row blocks: eval 4.01 /
-// 4.11 ms, train 15.9 / 15.5 ms (tools/gpu_r5_bound_ab.sh r5rb).
+// weights in LDS (64 channels) it always takes 2.  S2 with 1 / 4 row blocks: eval 4.01 /
+// 4.11 ms, train 15.9 / 15.5 ms.
 constexpr long kS1WideWgs = 4096;
 // row blocks of the 3-in-1 S2 (kS2Multi): 4 measured slower (300 registers, one wave per SIMD: train-mode
 // step 12.9 -> 13.1 ms)
-#ifndef MVS_S2M_RB
-#define MVS_S2M_RB 2
-#endif
 static int split_rb(int mode, int B, const int* on, int CO) {
-  if (mode == kS2 && CO == kS2Multi) return MVS_S2M_RB;
-  if (mode == kS1 && CO == 64 && MVS_S1_BLDS) return 2;
+  if (mode == kS2 && CO == kS2Multi) return 2;
+  if (mode == kS1 && CO == 64) return 2;
   if (mode != kS1) return 2;
   const long rows = (long)B * on[0] * on[1] * on[2];
   return rows >= kS1WideWgs * (kBlock / 64) * 16 * 4 ? 4 : 2;
@@ -950,7 +937,7 @@ int launch_conv3d_region_split(int mode, bool out_cf, const float* x, const floa
                                      x2_bound, y_bound, s);                                                \
     return MVS_OK;                                                                                         \
   }
-  // S1: conv_k_1 (16 / 32 / 64 channels; LDS-staged operands per MVS_S1_LDS); T2: deconv_3_0 (64 -> 32),
+  // S1: conv_k_1 (16 / 32 / 64 channels; LDS-staged operands per kS1Lds); T2: deconv_3_0 (64 -> 32),
   // deconv_2_0 (32 -> 16); S2: conv_k_0 from the split cost volume (32 -> 16 / 32 / 64)
   if (in_bn && !split_t2_lds(mode, B, CI, CO, on, per_lane, x2 != nullptr, true) &&
       !(split_uses_lds(mode, CI, CO, per_lane, x2 != nullptr) && CI <= 64))

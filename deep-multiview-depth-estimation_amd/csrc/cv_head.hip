@@ -25,8 +25,8 @@
 //     step later and applies BN_1 + ReLU; then all four form the sampling state of the batch after next
 //     and copy the tile's voxels inside conv_2_0's input box from the ring to the split cost volume
 //     (SCV, split.h).  The producers issue nothing but in-range gathers (see items()).
-// Per step: producers ~6.6k cycles of gathers + variance, consumers ~4k of MFMA (stamps,
-// tools/dbg/stamps.py): the producers' gather latency is the critical path.
+// Per step: producers ~6.6k cycles of gathers + variance, consumers ~4k of MFMA (measured with
+// per-segment clock stamps): the producers' gather latency is the critical path.
 // Results are bit-identical to the materialising path (fused forward -> SCV -> conv3d_split /
 // conv3d_s2_split): the same operands meet the same MFMAs in the same order.
 #include "launchers.h"
@@ -34,11 +34,6 @@
 #include "split.h"
 
 #include <algorithm>
-#ifdef MVS_HEAD_STAMP
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-#endif
 
 namespace mvs {
 namespace {
@@ -57,43 +52,21 @@ constexpr int kRing = 6;                                 // 4 planes read + 2 be
 constexpr int kRingB = kRing * kSlotB;                   // 82,944 B
 // PRESPLIT: the producers run AHEAD batches ahead of the step they fill for (2 more slots each), so
 // a slow load batch does not stall the consumers at the next barrier
-#ifndef MVS_HEAD_PRE_AHEAD
-#define MVS_HEAD_PRE_AHEAD 1
-#endif
-constexpr int kPreAhead = MVS_HEAD_PRE_AHEAD;
+constexpr int kPreAhead = 1;
 template <bool PRE>
 constexpr int ring_slots() {
   return PRE ? kRing + 2 * kPreAhead : kRing;
 }
 constexpr int kW1B = 27 * 2 * 64 * 16;                   // conv_1_0 fragments: 55,296 B
 constexpr int kScrB = 2 * 3 * 64 * 16;                   // conv_1_0 partials, double buffered
-#ifndef MVS_HEAD_ZC
-#define MVS_HEAD_ZC 48
-#endif
-constexpr int kZC = MVS_HEAD_ZC;                         // output depths per workgroup (even)
+constexpr int kZC = 48;                                  // output depths per workgroup (even)
 constexpr int kThreads = 512;
 constexpr int kPlaneItems = kHV * kC4;                   // 864 (voxel, quad) items per plane
 constexpr int kBatchItems = 2 * kPlaneItems;             // two planes per step
 constexpr int kItems = (kBatchItems + 255) / 256;        // 7 per producer thread
-#ifndef MVS_HEAD_KPF
-#define MVS_HEAD_KPF 3
-#endif
-constexpr int kPF = MVS_HEAD_KPF;                        // conv_0_0 A-fragment prefetch (items)
-#ifndef MVS_HEAD_PD
-#define MVS_HEAD_PD 1
-#endif
-constexpr int kPD = MVS_HEAD_PD;                         // PRESPLIT: batches of loads in flight
-#ifndef MVS_HEAD_VFAST
-#define MVS_HEAD_VFAST 1
-#endif
-constexpr bool kPreVoxelFast = MVS_HEAD_VFAST;
-// the sampling state of a batch is formed by the CONSUMER waves after their matrix work (they wait at
-// the step barrier otherwise; the producers' gathers are the step's critical path: cfg 2 2.28 -> 2.19 ms)
-#ifdef MVS_HEAD_COORDS_BY_PRODUCERS   // experiment (DESIGN.md §3.7 residual): the producers form their own sampling state
-constexpr bool kCoordsByConsumers = false;
-#else
-constexpr bool kCoordsByConsumers = true;
-#endif
+constexpr int kPF = 3;                                   // conv_0_0 A-fragment prefetch (items)
+constexpr int kPD = 1;                                   // PRESPLIT: batches of loads in flight
+constexpr bool kPreVoxelFast = true;                     // PRESPLIT: item order of the copy (see meta[])
 
 template <int NS, bool PRE = false>
 constexpr int coord_bytes() {   // [2 buffers][2 planes][NS views][108 voxels] x {off, wx, wy, -}
@@ -128,14 +101,7 @@ struct HeadArgs {
   int pad[3];                 // (z, y, x), odd
   int o0[3], on[3];           // conv_1_0 output region
   int r0[3], r1[3];           // SCV box [r0, r1)
-#ifdef MVS_HEAD_STAMP
-  unsigned long long* stamps;   // diagnostic build: [kStampWG][8 waves][kStampN] s_memtime stamps
-#endif
 };
-
-#ifdef MVS_HEAD_STAMP
-constexpr int kStampWG = 512, kStampN = 128;
-#endif
 
 __device__ inline float ror8(float v) {   // value of lane (l ^ 8) inside each 16-lane row
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xF, 0xF, false));
@@ -173,21 +139,6 @@ __global__ __launch_bounds__(kThreads) void cv_head_kernel(HeadArgs a) {
   // the wave index through readfirstlane: role branches are scalar (s_cbranch_scc), not exec-masked
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const bool consumer = wave < 4;
-#ifdef MVS_HEAD_STAMP
-  // diagnostic: lane 0 of every wave of the first kStampWG workgroups stamps s_memtime at segment ends
-  unsigned long long* const stp = wk < kStampWG ? a.stamps + ((size_t)wk * 8 + wave) * kStampN : nullptr;
-  int sti = 0;
-  auto stamp = [&]() {
-    __builtin_amdgcn_sched_barrier(0);
-    unsigned long long t;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    if (stp && lane == 0 && sti < kStampN) stp[sti] = t;
-    ++sti;
-  };
-#else
-  auto stamp = [&]() {};
-#endif
 
   // conv_1_0 weight fragments -> LDS (every thread)
   if constexpr (!PRE) {
@@ -227,10 +178,12 @@ __global__ __launch_bounds__(kThreads) void cv_head_kernel(HeadArgs a) {
   }
   // plane-independent per-lane constants of the coordinate jobs: halo voxels lane and lane + 64, their
   // kornia-normalised reference coordinates (norm_coord: two IEEE divisions each, formed once) and
-  // whether they lie in the image
+  // whether they lie in the image.  The sampling state of a batch is formed by the CONSUMER waves after
+  // their matrix work (they wait at the step barrier otherwise; the producers' gathers are the step's
+  // critical path: cfg 2 2.28 -> 2.19 ms)
   float cxn[2] = {0.f, 0.f}, cyn[2] = {0.f, 0.f};
   bool cin[2] = {false, false};
-  if (kCoordsByConsumers == consumer && !PRE) {
+  if (consumer && !PRE) {
 #pragma unroll
     for (int pass = 0; pass < 2; ++pass) {
       const int v = lane + 64 * pass;
@@ -285,10 +238,7 @@ __global__ __launch_bounds__(kThreads) void cv_head_kernel(HeadArgs a) {
   // in range (an out-of-range load returns at once and made hazard 1 of DESIGN.md §3.7 frequent).
   // (Measured and dropped: skipping the items of edge tiles whose 64 lanes lie outside the image --
   // 2.34 against 2.18 ms, the extra branches cost the interior tiles more than the edges save.)
-#ifndef MVS_HEAD_AHEAD
-#define MVS_HEAD_AHEAD 2
-#endif
-  constexpr int kAhead = MVS_HEAD_AHEAD;
+  constexpr int kAhead = 2;
   // per-item constants (the same every batch), packed: LDS offset inside a ring slot (bits 0-12), in
   // the image (13), plane of the batch (15), quad (16-18), halo voxel (19-25)
   uint32_t meta[kItems];
@@ -298,7 +248,7 @@ __global__ __launch_bounds__(kThreads) void cv_head_kernel(HeadArgs a) {
       const int e = min(ptid + 256 * u, kBatchItems - 1);
       const int pl = e >= kPlaneItems ? 1 : 0;
       const int r = e - pl * kPlaneItems;
-      // PRE (MVS_HEAD_VFAST): voxel fastest, so a wave's 64 loads are runs of one quad plane (rows of
+      // PRE (kPreVoxelFast): voxel fastest, so a wave's 64 loads are runs of one quad plane (rows of
       // 18 x 16 B) instead of 8 voxels x 8 quad planes 2^22 B apart
       const bool vfast = PRE && kPreVoxelFast;
       const int v = vfast ? r % kHV : r >> 3, q = vfast ? r / kHV : r & 7;
@@ -322,9 +272,6 @@ __global__ __launch_bounds__(kThreads) void cv_head_kernel(HeadArgs a) {
   uint32_t pok[kPD];     // bit u: item u of the buffered batch is valid
   const int pnu = __builtin_amdgcn_readfirstlane(ptid + 256 * (kItems - 1) < kBatchItems ? kItems : kItems - 1);
   auto pre_load = [&](int j, int pb) {
-#ifdef MVS_HEAD_NO_LOAD   // (timing ablation: the ring is never filled)
-    return;
-#endif
     const int pbase = z0 - 1 + 2 * j;
     pok[pb] = 0;
 #pragma unroll
@@ -342,9 +289,6 @@ __global__ __launch_bounds__(kThreads) void cv_head_kernel(HeadArgs a) {
     }
   };
   auto pre_store = [&](int j, int pb) {
-#ifdef MVS_HEAD_NO_LOAD
-    return;
-#endif
     const int sl0 = slot_of(z0 - 1 + 2 * j);
 #pragma unroll
     for (int u = 0; u < kItems; ++u) {
@@ -380,11 +324,7 @@ __global__ __launch_bounds__(kThreads) void cv_head_kernel(HeadArgs a) {
 #pragma unroll
       for (int s = 0; s < NS; ++s) {
         const uint4 ce = *reinterpret_cast<const uint4*>(coord + (((tb * 2 + pl) * NS + s) * kHV + v) * 16);
-#ifdef MVS_HEAD_RDC128   // experiment: all four words used (ce.w == 0), so the read is a ds_read_b128, not b96
-        co[u & 1][s] = ce.x | ce.w;
-#else
         co[u & 1][s] = ce.x;
-#endif
         cx[u & 1][s] = __uint_as_float(ce.y);
         cy[u & 1][s] = __uint_as_float(ce.z);
       }
@@ -397,39 +337,10 @@ __global__ __launch_bounds__(kThreads) void cv_head_kernel(HeadArgs a) {
         const uint32_t o = co[u & 1][s] + qo;
         fx[rr][s] = cx[u & 1][s];
         fy[rr][s] = cy[u & 1][s];
-#ifdef MVS_HEAD_ABL_G
-        {
-          const float f = __uint_as_float(o);
-          tp[rr][s][0] = f4v{f, f, f, f};
-          tp[rr][s][1] = f4v{f, 1.f, f, f};
-          tp[rr][s][2] = f4v{f, f, 2.f, f};
-          tp[rr][s][3] = f4v{f, f, f, 3.f};
-        }
-#elif defined(MVS_HEAD_X2)   // experiment: each 16-byte tap as two 8-byte loads
-        {
-          typedef __attribute__((ext_vector_type(2))) unsigned v2u;
-          const uint32_t offs[4] = {o, o + pstride, o + (uint32_t)pg.pitch * pstride, o + (uint32_t)pg.pitch * pstride + pstride};
-#pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            const v2u a0 = __builtin_amdgcn_raw_buffer_load_b64(rsv[s], (int)offs[t], 0, 0);
-            const v2u a1 = __builtin_amdgcn_raw_buffer_load_b64(rsv[s], (int)(offs[t] + 8u), 0, 0);
-            tp[rr][s][t] = f4v{__uint_as_float(a0.x), __uint_as_float(a0.y), __uint_as_float(a1.x), __uint_as_float(a1.y)};
-          }
-        }
-#elif defined(MVS_HEAD_GLOBAL)   // experiment: taps through global (flat-space) loads instead of buffer loads
-        {
-          const char* gb = reinterpret_cast<const char*>(a.packed) + (size_t)(b * V + 1 + s) * pg.plane * pstride;
-          tp[rr][s][0] = *reinterpret_cast<const f4v*>(gb + o);
-          tp[rr][s][1] = *reinterpret_cast<const f4v*>(gb + o + pstride);
-          tp[rr][s][2] = *reinterpret_cast<const f4v*>(gb + o + (uint32_t)pg.pitch * pstride);
-          tp[rr][s][3] = *reinterpret_cast<const f4v*>(gb + o + (uint32_t)pg.pitch * pstride + pstride);
-        }
-#else
         tp[rr][s][0] = ld4(rsv[s], o, 0);
         tp[rr][s][1] = ld4(rsv[s], o + pstride, 0);
         tp[rr][s][2] = ld4(rsv[s], o + (uint32_t)pg.pitch * pstride, 0);
         tp[rr][s][3] = ld4(rsv[s], o + (uint32_t)pg.pitch * pstride + pstride, 0);
-#endif
       }
     };
     // items that exist for this wave: u < nu (wave-uniform)
@@ -453,11 +364,6 @@ __global__ __launch_bounds__(kThreads) void cv_head_kernel(HeadArgs a) {
     lds_drain();
 #pragma unroll
     for (int u = 0; u < kAhead; ++u) issue(u);
-#ifdef MVS_HEAD_RDC_FIRST
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-#endif
     rdc(kAhead);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -468,14 +374,6 @@ __global__ __launch_bounds__(kThreads) void cv_head_kernel(HeadArgs a) {
       const int p = pbase + pl;
       const bool valid = (m & (1u << 13)) && (unsigned)p < (unsigned)D;
       const int rr = u % (kAhead + 1);
-#ifdef MVS_HEAD_VMWAIT   // experiment: item u's gathers explicitly waited for (item u + 1's may stay in flight), then nops
-      __builtin_amdgcn_sched_barrier(0);
-      if (kAhead > 1 && has(u + 1))
-        asm volatile("s_waitcnt vmcnt(%0)\n\ts_nop %1" ::"n"(4 * NS), "n"(MVS_HEAD_VMWAIT) : "memory");
-      else
-        asm volatile("s_waitcnt vmcnt(0)\n\ts_nop %0" ::"n"(MVS_HEAD_VMWAIT) : "memory");
-      __builtin_amdgcn_sched_barrier(0);
-#endif
       f4v xs[NS];
 #pragma unroll
       for (int s = 0; s < NS; ++s) xs[s] = bilerp(tp[rr][s], fx[rr][s], fy[rr][s]);
@@ -484,27 +382,18 @@ __global__ __launch_bounds__(kThreads) void cv_head_kernel(HeadArgs a) {
       split4(acc, ex, hi, lo);
       if (!valid) hi = lo = make_uint2(0u, 0u);
       lds_drain();
-#ifdef MVS_HEAD_RDC_FIRST   // experiment: item u + kAhead + 1's sampling-state read before (not under) u + kAhead's gathers
-      if (has(u + kAhead + 1)) rdc(u + kAhead + 1);
-      lds_drain();
-      if (has(u + kAhead)) issue(u + kAhead);
-#else
       if (has(u + kAhead)) issue(u + kAhead);
       if (has(u + kAhead + 1)) rdc(u + kAhead + 1);
-#endif
       char* dst = ring + (sl0 + pl) * kSlotB + (m & 0x1FFFu);
       // THE HAZARD: the item's two ds_write_b64 ring stores must not run while
       // any of this wave's tap gathers (buffer_load_dwordx4) is still in flight, and must complete before
       // the wave's next VALU work.  With gathers of later items outstanding across the stores, the last
       // 16-lane group of a ds_write_b64 (lanes 48-63, serviced last) stored wrong data in some launches
       // (bench geometry: 20 of 20 launches at V = 2 and V = 3); a wait for the stores alone cured V = 2,
-      // not V = 3; both waits: 0 of 20 at every geometry (tools/dbg/stress_r6.sh, gpurun_out r6b / r6c).
+      // not V = 3; both waits: 0 of 20 at every geometry.
       __builtin_amdgcn_sched_barrier(0);
 #ifndef MVS_HEAD_NO_STORE_FENCE   // (mutation build of tests/test_head_isa.py only: the rule's checker must fail)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-#ifdef MVS_HEAD_STORE_NOP   // experiment (DESIGN.md §3.7 residual): wait states between the item's VALU and its ring stores
-      asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");
 #endif
       __builtin_amdgcn_sched_barrier(0);
       *reinterpret_cast<uint2*>(dst) = hi;
@@ -604,11 +493,7 @@ __global__ __launch_bounds__(kThreads) void cv_head_kernel(HeadArgs a) {
   // conv_1_0 in step k: window zs - 1 completes (depth tap 2 on plane zs + 1), window zs + 1 starts
   auto conv1_step = [&](int k) {
     const int zs = z0 + 2 * k;
-#if defined(MVS_HEAD_ABL_C) || defined(MVS_HEAD_NO_MAC1)
-    if (false) {
-#else
     if (c1w < 3) {
-#endif
       if (k == 0) {
         mac1(cur, slot_of(z0 - 1), 0);
         mac1(cur, slot_of(z0), 1);
@@ -641,13 +526,10 @@ __global__ __launch_bounds__(kThreads) void cv_head_kernel(HeadArgs a) {
     // (its slots were last read in step k - 1), its loads issued kPD steps earlier (buffer j % kPD:
     // the step loop unrolled by kPD keeps the index static)
     constexpr int A = kPreAhead;
-    stamp();
     pre_load(0, 0);
     load_bw1();
     load_bn1();
-    stamp();
     __syncthreads();
-    stamp();
     pre_store(0, 0);
 #pragma unroll
     for (int j = 1; j <= 1 + A; ++j) {
@@ -658,12 +540,8 @@ __global__ __launch_bounds__(kThreads) void cv_head_kernel(HeadArgs a) {
 #pragma unroll
     for (int r = 0; r < kPD; ++r)
       if (2 + A + r < nbatch) pre_load(2 + A + r, (2 + A + r) % kPD);
-    stamp();
     __syncthreads();
-    stamp();
-    stamp();
     __syncthreads();
-    stamp();
     for (int k0 = 0; k0 < nsteps; k0 += kPD) {
 #pragma unroll
       for (int r = 0; r < kPD; ++r) {
@@ -671,41 +549,22 @@ __global__ __launch_bounds__(kThreads) void cv_head_kernel(HeadArgs a) {
         if (k >= nsteps) break;   // uniform
         if (k + 2 + A < nbatch) pre_store(k + 2 + A, (r + 2 + A) % kPD);
         if (k + 2 + A + kPD < nbatch) pre_load(k + 2 + A + kPD, (r + 2 + A) % kPD);
-        stamp();
         conv1_step(k);
-        stamp();
         __syncthreads();
-        stamp();
       }
     }
     conv1_tail();
     return;
   }
   if (!consumer) {
-    stamp();
-    if (!kCoordsByConsumers) {
-      coords(0, 0);
-      coords(1, 1);
-    }
-    stamp();
     __syncthreads();
-    stamp();
     items(0, 0);
     items(1, 1);
-    stamp();
     __syncthreads();
-    stamp();
-    if (!kCoordsByConsumers && 2 < nbatch) coords(2, 0);   // buffer 0 is free again (batch 0's items are done)
-    stamp();
     __syncthreads();
-    stamp();
     for (int k = 0; k < nsteps; ++k) {
       if (k + 2 < nbatch) items(k + 2, (k + 2) & 1);
-      stamp();
-      if (!kCoordsByConsumers && k + 3 < nbatch) coords(k + 3, (k + 3) & 1);
-      stamp();
       __syncthreads();
-      stamp();
     }
     __syncthreads();
     return;
@@ -760,29 +619,16 @@ __global__ __launch_bounds__(kThreads) void cv_head_kernel(HeadArgs a) {
             0, 0);
     }
   };
-  stamp();
-  if (kCoordsByConsumers) {
-    coords(0, 0);
-    coords(1, 1);
-  }
-  stamp();
+  coords(0, 0);
+  coords(1, 1);
   __syncthreads();
-  stamp();
-  stamp();
   __syncthreads();
-  stamp();
-  if (kCoordsByConsumers && 2 < nbatch) coords(2, 0);
-  stamp();
+  if (2 < nbatch) coords(2, 0);   // buffer 0 is free again (batch 0's items are done)
   __syncthreads();
-  stamp();
   for (int k = 0; k < nsteps; ++k) {
     const int zs = z0 + 2 * k;
     // ---- conv_0_0 on planes zs - 1 .. zs + 2 (conv3d_split.hip's item order) ----
-#if defined(MVS_HEAD_ABL_C) || defined(MVS_HEAD_NO_C0)   // (timing ablations)
-    if (false) {
-#else
     if (row_on) {
-#endif
       f4 ah[2], al[2];
 #pragma unroll
       for (int d = 0; d < 2; ++d) {
@@ -840,16 +686,13 @@ __global__ __launch_bounds__(kThreads) void cv_head_kernel(HeadArgs a) {
         }
       }
     }
-    stamp();
     if constexpr (!PRE) conv1_step(k);
-    if (kCoordsByConsumers && k + 3 < nbatch) coords(k + 3, (k + 3) & 1);
+    if (k + 3 < nbatch) coords(k + 3, (k + 3) & 1);
     // batch k + 1's planes (and plane z0 of batch 0) to the box: resident in their slots this step
     if (k == 0) box_store(z0);
     box_store(zs + 1);
     box_store(zs + 2);
-    stamp();
     __syncthreads();
-    stamp();
   }
   if constexpr (PRE) __syncthreads();   // (the producers' conv1_tail barrier)
   else conv1_tail();
@@ -985,30 +828,12 @@ int launch_cv_head(const Geometry& g, const float* feat, const Cams& cm, float* 
   a.w_exp1 = w_exp1;
   const int gst = head_grid(g, a, pad, o0, on, r0, r1);
   if (gst != MVS_OK) return gst;
-#ifdef MVS_HEAD_STAMP
-  static unsigned long long* stamps = nullptr;
-  const size_t stamp_bytes = (size_t)kStampWG * 8 * kStampN * sizeof(unsigned long long);
-  if (!stamps) (void)hipMalloc(&stamps, stamp_bytes);
-  (void)hipMemsetAsync(stamps, 0, stamp_bytes, s);
-  a.stamps = stamps;
-#endif
   if (ev0) (void)hipEventRecord(ev0, s);
   if (g.V == 2)
     hipLaunchKernelGGL(cv_head_kernel<2>, xcd_grid(a.total), dim3(kThreads), 0, s, a);
   else
     hipLaunchKernelGGL(cv_head_kernel<3>, xcd_grid(a.total), dim3(kThreads), 0, s, a);
   if (ev1) (void)hipEventRecord(ev1, s);
-#ifdef MVS_HEAD_STAMP
-  if (const char* path = getenv("MVS_HEAD_STAMPS")) {   // diagnostic build only: synchronous dump
-    std::vector<unsigned long long> h(stamp_bytes / sizeof(unsigned long long));
-    (void)hipStreamSynchronize(s);
-    (void)hipMemcpy(h.data(), stamps, stamp_bytes, hipMemcpyDeviceToHost);
-    if (FILE* f = fopen(path, "ab")) {
-      fwrite(h.data(), 1, stamp_bytes, f);
-      fclose(f);
-    }
-  }
-#endif
   launch_head_faces(g, a, bn1, y1, pad, o0, on, s);
   return MVS_OK;
 }
@@ -1038,27 +863,9 @@ int launch_split_head(const Geometry& g, const void* scv_in, const uint32_t* abs
   const int zero[3] = {0, 0, 0};
   const int gst = head_grid(g, a, pad, o0, on, zero, zero);
   if (gst != MVS_OK) return gst;
-#ifdef MVS_HEAD_STAMP
-  static unsigned long long* stamps = nullptr;
-  const size_t stamp_bytes = (size_t)kStampWG * 8 * kStampN * sizeof(unsigned long long);
-  if (!stamps) (void)hipMalloc(&stamps, stamp_bytes);
-  (void)hipMemsetAsync(stamps, 0, stamp_bytes, s);
-  a.stamps = stamps;
-#endif
   if (ev0) (void)hipEventRecord(ev0, s);
   hipLaunchKernelGGL((cv_head_kernel<2, true>), xcd_grid(a.total), dim3(kThreads), 0, s, a);
   if (ev1) (void)hipEventRecord(ev1, s);
-#ifdef MVS_HEAD_STAMP
-  if (const char* path = getenv("MVS_HEAD_STAMPS")) {   // diagnostic build only: synchronous dump
-    std::vector<unsigned long long> h(stamp_bytes / sizeof(unsigned long long));
-    (void)hipStreamSynchronize(s);
-    (void)hipMemcpy(h.data(), stamps, stamp_bytes, hipMemcpyDeviceToHost);
-    if (FILE* f = fopen(path, "ab")) {
-      fwrite(h.data(), 1, stamp_bytes, f);
-      fclose(f);
-    }
-  }
-#endif
   launch_head_faces(g, a, bn1, y1, pad, o0, on, s, y1_bound);
   return MVS_OK;
 }

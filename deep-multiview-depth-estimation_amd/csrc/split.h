@@ -79,10 +79,7 @@ __device__ inline int act_split_exponent(float bound) {
 // raise the bound words by this wave's max |v| (m >= 0 per lane; whole wave).  kCheck: read the slot
 // first (the read's round trip holds the wave: for epilogues at a kernel's end; a persistent kernel's
 // mid-loop update, cv_head.hip, sends the atomic unconditionally)
-#ifndef MVS_BOUND_CHECK
-#define MVS_BOUND_CHECK 1
-#endif
-template <bool kCheck = (MVS_BOUND_CHECK != 0)>
+template <bool kCheck = true>
 __device__ inline void bound_update(uint32_t* __restrict__ words, float m) {
   uint32_t v = __float_as_uint(m);
 #pragma unroll
