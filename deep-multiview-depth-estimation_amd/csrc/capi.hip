@@ -210,6 +210,18 @@ int deconv3d_bwd_geometry(int batch, int c_in, int c_out, const int* in_size, co
   return stride2_bwd_geometry(batch, in_size, out_size, crop, true, c_out);
 }
 
+// MVS_OK when the 2-D convolutions' weight / input gradient can launch: a shape with kernels, element counts of x and
+// gy below 2^31 (32-bit tile and staging indices; offsets are 64-bit)
+int conv2d_bwd_geometry(int n, int c_in, int c_out, int h, int w, int k, int stride) {
+  if (n <= 0 || h <= 0 || w <= 0 || !mvs::conv2d_bwd_supported(c_in, c_out, k, stride)) return MVS_ERR_INVALID_ARGUMENT;
+  const uint64_t ho = (uint64_t)((h + 2 * (k / 2) - k) / stride + 1), wo = (uint64_t)((w + 2 * (k / 2) - k) / stride + 1);
+  // (factor by factor: no product of two of these passes 2^64)
+  const uint64_t lim = 1ull << 31, hw = (uint64_t)h * (uint64_t)w, ohw = ho * wo;
+  if (hw >= lim || hw * (uint64_t)c_in >= lim || hw * (uint64_t)c_in * (uint64_t)n >= lim) return MVS_ERR_TOO_LARGE;
+  if (ohw >= lim || ohw * (uint64_t)c_out >= lim || ohw * (uint64_t)c_out * (uint64_t)n >= lim) return MVS_ERR_TOO_LARGE;
+  return MVS_OK;
+}
+
 // the entry points' prologue and epilogue: `ok` (pointers, flags), then the geometry's status, then (the input
 // gradients: grid.z) the batch bound, then the launch under a LaunchCheck
 template <class Launch>
@@ -787,6 +799,37 @@ int mvs_deconv3d_k3s2_dgrad(const float* gy, const float* w27, int flags, int ba
                                                    crop, out_size, (hipStream_t)stream);
                         return MVS_OK;
                       });
+}
+
+int mvs_conv2d_wgrad_plan(int n, int c_in, int c_out, int h, int w, int k, int stride, int* tiles, int* slots) {
+  const int g = conv2d_bwd_geometry(n, c_in, c_out, h, w, k, stride);
+  if (g != MVS_OK) return g;
+  const mvs::Conv2dWgradPlan p = mvs::conv2d_wgrad_plan(n, c_in, c_out, h, w, k, stride);
+  if (tiles) *tiles = p.tiles;
+  if (slots) *slots = p.slots;
+  return MVS_OK;
+}
+
+size_t mvs_conv2d_wgrad_workspace_bytes(int n, int c_in, int c_out, int h, int w, int k, int stride) {
+  if (conv2d_bwd_geometry(n, c_in, c_out, h, w, k, stride) != MVS_OK) return 0;
+  const mvs::Conv2dWgradPlan p = mvs::conv2d_wgrad_plan(n, c_in, c_out, h, w, k, stride);
+  return (size_t)p.slots * p.slot_floats * sizeof(float);
+}
+
+int mvs_conv2d_wgrad(const float* x, const float* gy, int n, int c_in, int c_out, int h, int w, int k, int stride,
+                     float* dw, float* workspace, void* stream) {
+  return train_launch(aligned16(x, gy, dw, workspace), conv2d_bwd_geometry(n, c_in, c_out, h, w, k, stride), false, n,
+                      [&] {
+                        return mvs::launch_conv2d_wgrad(x, gy, n, c_in, c_out, h, w, k, stride, workspace, dw,
+                                                        (hipStream_t)stream);
+                      });
+}
+
+int mvs_conv2d_dgrad(const float* gy, const float* weight, int n, int c_in, int c_out, int h, int w, int k,
+                     int stride, float* gx, void* stream) {
+  return train_launch(aligned16(gy, weight, gx), conv2d_bwd_geometry(n, c_in, c_out, h, w, k, stride), true, n, [&] {
+    return mvs::launch_conv2d_dgrad(gy, weight, gx, n, c_in, c_out, h, w, k, stride, (hipStream_t)stream);
+  });
 }
 
 int mvs_conv_head_fp32_fwd(const float* cv4, int batch, int d, int h, int w, const float* w0_wz,

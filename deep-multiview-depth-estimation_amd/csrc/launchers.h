@@ -156,6 +156,20 @@ int launch_conv2d_narrow(const float* in, const float* wt, float* out, int N, in
                          int K, int stride, const float* bn_scale, const float* bn_shift, const float* bn_mean,
                          uint32_t* y_bound, hipStream_t s);
 
+// conv2d_bwd.hip: the same layers' gradients under autograd (x, gy, gx NCHW fp32 read / written in place, the
+// weight [c_out][c_in][k][k]; conv2d_bwd_supported: launch_conv2d_narrow's eight shapes).  dgrad: every element of gx written,
+// N in grid.y.  wgrad: dw [c_out][c_in][k][k] from a workspace `part` of plan.slots * plan.slot_floats floats
+// (persistent workgroups over plan.tiles 32 x 8 output tiles, one slot each, reduced in slot order)
+struct Conv2dWgradPlan {
+  int tiles, slots, slot_floats;
+};
+bool conv2d_bwd_supported(int Cin, int Cout, int K, int stride);
+Conv2dWgradPlan conv2d_wgrad_plan(int N, int Cin, int Cout, int H, int W, int K, int stride);
+int launch_conv2d_dgrad(const float* gy, const float* w, float* gx, int N, int Cin, int Cout, int H, int W, int K,
+                        int stride, hipStream_t s);
+int launch_conv2d_wgrad(const float* x, const float* gy, int N, int Cin, int Cout, int H, int W, int K, int stride,
+                        float* part, float* dw, hipStream_t s);
+
 // conv2d_split.hip: the same convolutions (8..32 input channels) on the f16 matrix cores with split
 // operands; x scaled by its bound words, y's bound words raised; weight fragments from
 // mvs_conv2d_split_weights (conv2d_split_kblocks K-32 blocks)

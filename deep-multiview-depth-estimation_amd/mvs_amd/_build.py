@@ -19,7 +19,7 @@ SOURCES = [os.path.join(CSRC, f) for f in ("capi.hip", "plane_sampling.hip", "co
                                            "conv3d_wgrad.hip", "conv3d_s2_lds.hip",
                                            "conv3d_region_wgrad.hip", "conv3d_s2_wgrad.hip",
                                            "conv3d_t2_wgrad.hip", "deconv3d_region_bwd.hip",
-                                           "bn_train_bwd.hip")]
+                                           "bn_train_bwd.hip", "conv2d_bwd.hip")]
 HEADERS = [os.path.join(REPO_ROOT, "include", "mvs_cost_volume.h"),
            os.path.join(REPO_ROOT, "include", "train", "mvs_region_train.h"),
            os.path.join(CSRC, "common.h"), os.path.join(CSRC, "launchers.h"),
@@ -33,8 +33,11 @@ HEADERS = [os.path.join(REPO_ROOT, "include", "mvs_cost_volume.h"),
 # 0.  Elementwise identical arithmetic (a packed FMA is two fmaf): the outputs keep
 # their bits.  The train-mode BN backward (bn_train_bwd.hip) is built the same way: its reduce kernels store to
 # LDS next to fp32 code the compiler would pair, the pattern above; they are HBM-bound, so it costs nothing.
+# The 2-D convolutions' gradients (conv2d_bwd.hip) likewise: both kernels stage the next pass into LDS inside the
+# loop that holds their fp32 chains; the chains are scalar fmaf per channel / MFMA, so nothing is lost.
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-SOURCE_FLAGS = {"cv_head.hip": _NO_PACKED_FP32, "bn_train_bwd.hip": _NO_PACKED_FP32}
+SOURCE_FLAGS = {"cv_head.hip": _NO_PACKED_FP32, "bn_train_bwd.hip": _NO_PACKED_FP32,
+                "conv2d_bwd.hip": _NO_PACKED_FP32}
 OUTPUT = os.path.join(_HERE, "libmvs_cost_volume.so")
 ARCH = os.environ.get("MVS_OFFLOAD_ARCH", "gfx950")
 

@@ -124,6 +124,10 @@ TRAIN_SIGNATURES = {
     "mvs_bn_relu_bwd_slots": (ctypes.c_size_t, [_c_int, _c_int, _c_int, _p, _p, _p]),
     "mvs_bn_relu_bwd_reduce": (_c_int, [_p, _p, _c_int, _c_int, _c_int] + [_p] * 8),
     "mvs_bn_relu_bwd_apply": (_c_int, [_p, _p, _c_int, _c_int, _c_int] + [_p] * 10),
+    "mvs_conv2d_wgrad_plan": (_c_int, [_c_int] * 7 + [_p, _p]),
+    "mvs_conv2d_wgrad_workspace_bytes": (ctypes.c_size_t, [_c_int] * 7),
+    "mvs_conv2d_wgrad": (_c_int, [_p, _p] + [_c_int] * 7 + [_p, _p, _p]),
+    "mvs_conv2d_dgrad": (_c_int, [_p, _p] + [_c_int] * 7 + [_p, _p]),
 }
 
 

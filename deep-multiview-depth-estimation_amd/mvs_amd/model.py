@@ -58,6 +58,15 @@ def _conv_bn_relu_stack(spec, device):
     return nn.Sequential(*layers)
 
 
+def conv2d_bwd_mode():
+    """MVS_TRAIN_CONV2D_BWD, read once per _run_stack call: "hip" (mvs_amd/conv2d_train.py) or "taps" (the per-tap
+    GEMMs; the default, also when unset or empty); anything else raises.  A switch of its own."""
+    v = os.environ.get("MVS_TRAIN_CONV2D_BWD", "") or "taps"
+    if v not in ("hip", "taps"):
+        raise ValueError("MVS_TRAIN_CONV2D_BWD must be 'hip' or 'taps', got %r" % (v,))
+    return v
+
+
 def _run_stack(seq, x, split_f16=False):
     """A conv -> BatchNorm -> ReLU stack (encoder / refinement).  In fp32 no-grad inference on the
     GPU the convolutions run on the direct HIP kernel (mvs::conv2d, csrc/conv2d_narrow.hip: exact fp32)
@@ -72,8 +81,15 @@ def _run_stack(seq, x, split_f16=False):
         from . import tap_gemm
         from .ops import conv2d_supported
         hip_fwd = os.environ.get("MVS_TRAIN_CONV2D_FWD", "hip") == "hip"
+        # MVS_TRAIN_CONV2D_BWD=hip: both gradients on csrc/conv2d_bwd.hip too (conv2d_train.py; imported only then)
+        hip_bwd = None
+        if hip_fwd and conv2d_bwd_mode() == "hip":
+            from . import conv2d_train as hip_bwd
         for layer in seq:
             if isinstance(layer, nn.Conv2d) and hip_fwd and conv2d_supported(layer) and x.dim() == 4:
+                if hip_bwd is not None and hip_bwd.applies(layer, x):
+                    x = hip_bwd.conv2d_hip(x, layer)    # the HIP forward kernel, HIP input and weight gradients
+                    continue
                 x = tap_gemm.conv2d_hip_fwd(x, layer)   # the HIP forward kernel, per-tap-GEMM backward
             elif isinstance(layer, nn.Conv2d) and tap_gemm.conv2d_applies(layer):
                 x = tap_gemm.conv2d(x, layer.weight, layer.stride, layer.padding)

@@ -149,6 +149,35 @@ int mvs_bn_relu_bwd_apply(const float* z, const float* gy, int layout, int batch
                           const int* box_origin, const int* box_size, const float* scale, const float* shift,
                           const float* mean, const float* g_s1, const float* g_s2, float* gz, void* stream);
 
+/* Backward of the 2-D feature encoder's and refinement net's bias-free convolutions nn.Conv2d(c_in, c_out, k,
+ * stride, padding = k / 2, bias=False) (model.py:22-65, 134-145; forward: mvs_conv2d_fwd) under autograd
+ * (mvs_amd/conv2d_train.py).  (c_in, c_out, k, stride) is one of (3,8,3,1) (8,8,3,1) (8,16,5,2) (16,16,3,1)
+ * (16,32,5,2) (32,32,3,1) (4,32,3,1) (32,1,3,1): anything else is MVS_ERR_INVALID_ARGUMENT.
+ *   x, gx  [n][c_in][h][w]              NCHW, read / written in place
+ *   gy     [n][c_out][ho][wo]           NCHW, ho = (h + 2 (k / 2) - k) / stride + 1, wo alike
+ *   weight, dw [c_out][c_in][k][k]      nn.Conv2d's weight layout
+ * Every device pointer contiguous fp32 with a 16-byte-aligned base; n, h, w >= 1.  Index width: the element
+ * counts of x and of gy below 2^31 (else MVS_ERR_TOO_LARGE; offsets themselves are 64-bit), and for the input
+ * gradient n <= 65535 (else MVS_ERR_TOO_LARGE).  Arguments are checked before any launch: a refused call touches
+ * no memory.
+ *   dgrad: gx[n][ci][iy][ix] = sum over co, ky, kx of weight[co][ci][ky][kx] * gy[n][co][oy][ox] with
+ *          oy * stride + ky - k / 2 = iy (x alike): one owner per input pixel, fp32 fmaf chains in the order
+ *          co, ky, kx; no atomics, every element of gx written once.
+ *   wgrad: dw[co][ci][ky][kx] = sum over n, oy, ox of gy[n][co][oy][ox] * x[n][ci][oy * stride + ky - k / 2][..]:
+ *          fp32 on the f32-input matrix cores; persistent workgroups walk the 32 x 8 output tiles (tile t goes to
+ *          workgroup t mod slots) and store one partial slot each, written exactly once per launch; the slots are
+ *          summed in slot order (bit-reproducible; no atomics; the workspace need not be zeroed).
+ *   plan:  *tiles = n * ceil(ho / 8) * ceil(wo / 32), *slots = min(*tiles, 512); either pointer may be null.
+ *          Returns the status the weight gradient would (dimensions only).
+ *   workspace: mvs_conv2d_wgrad_workspace_bytes(...) = slots * c_in * 16 ceil(k k / 16) * 16 ceil(c_out / 16)
+ *          floats (0 for arguments the launch would refuse). */
+int mvs_conv2d_wgrad_plan(int n, int c_in, int c_out, int h, int w, int k, int stride, int* tiles, int* slots);
+size_t mvs_conv2d_wgrad_workspace_bytes(int n, int c_in, int c_out, int h, int w, int k, int stride);
+int mvs_conv2d_wgrad(const float* x, const float* gy, int n, int c_in, int c_out, int h, int w, int k, int stride,
+                     float* dw, float* workspace, void* stream);
+int mvs_conv2d_dgrad(const float* gy, const float* weight, int n, int c_in, int c_out, int h, int w, int k,
+                     int stride, float* gx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
