@@ -14,7 +14,10 @@
 //                     gathers inputs i = (o + P - t) / 2 for t of o + P's parity (1 or 2 taps per
 //                     dim); outputs are processed by parity class (8 launches' worth of grid.y), so
 //                     every voxel of a 16-voxel MFMA row block has the same taps; the input may be
-//                     the sum of two region tensors (model.py:119-121's `y3 + y2`, `y2 + y1`).
+//                     the sum of two region tensors (model.py:119-121's `y3 + y2`, `y2 + y1`).  That is
+//                     the class kernel (MVS_CONV_PER_LANE, the stacked input gradient); the forward's
+//                     default for 32 -> 16 is conv3d_t2_cells_kernel below, one pass per input cell,
+//                     bit-equal.
 // GEMM per sample: rows = output voxels of the region (flattened z, y, x; parity class for T2),
 // columns = output channels, K = (tap, input channel).  A wave owns 2 x 16 rows and every column
 // block (CO / 16); per (tap, 16-channel block) each lane loads 4 consecutive channels of its row's
@@ -310,6 +313,224 @@ void launch_mode(const float* x, const float* x2, const float* w, float* y, cons
                      x, x2, w, y, sc, sh, mu, g);
 }
 
+// ---- transposed convolutions, one register-tiled pass per input cell (deconv_2_0) ----
+// The class kernel above walks the output eight times, once per parity class, and every class fetches its
+// own taps' input voxels: over the classes each voxel's 16-channel block is loaded 27 times (54 with the
+// addend), and within a class consecutive rows are outputs two apart in x (4-byte stores with gaps the other
+// x parity fills from another workgroup).  Here a GEMM row is a CELL c = (o + P) >> 1 per dim: its 2 x 2 x 2
+// outputs 2 c - P + par read only the 2 x 2 x 2 inputs {c, c - 1}^3 (tap t = par + 2 j reads c - j), so the
+// lane loads each of them once and feeds all eight classes' accumulators from registers -- no LDS, no
+// barriers.  A wave owns RB row blocks of 16 consecutive cells along x (row blocks of every (cell-z, cell-y)
+// line, flattened); lane (m, kq) supplies channels cb * 16 + 4 kq + s of row m as in the class kernel.
+// Order: the tap rows (tz, ty) are visited by the input row (jz, jy) = (tz >> 1, ty >> 1) they read --
+// (0,0) (0,1) (1,0) (1,1) | (0,2) (1,2) | (2,0) (2,1) | (2,2) -- so only one input row (2 voxels x CI
+// channels per row block) is live at a time; within every class that is still ascending (tz, ty), then
+// channel block, then tx, then K-step: each accumulator sees the class kernel's products in the class
+// kernel's order, and every output is bit-equal to region_conv<kT2, ..., CLS>.  The eight classes' chains
+// are independent, which hides the dependent-MFMA latency the 1-tap class cannot hide on its own.
+// Epilogue (eval BN + ReLU; no bound words): lane (m, kq) holds, per channel and (pz, py), the 2 x 4 outputs of cells 4 kq .. 4 kq + 3: 8
+// consecutive x.  Channels-first they go out as 16-byte / 8-byte vectors on the address's alignment (single
+// dwords only at the two ends of a lane's run when it starts on an odd element, and at the region's edges);
+// channels-last as 16 lanes x 4 B per voxel, as the class kernel.
+typedef float f2v __attribute__((ext_vector_type(2)));
+
+// v[0 .. 8) to p[0 .. 8), elements lo <= i < hi only; A = (element index of p) mod 4
+template <int A>
+__device__ __forceinline__ void store_run8(float* __restrict__ p, const float (&v)[8], int lo, int hi) {
+  auto st1 = [&](int i) {
+    if (i >= lo && i < hi) p[i] = v[i];
+  };
+  auto st2 = [&](int i) {
+    if (i >= lo && i + 2 <= hi) *reinterpret_cast<f2v*>(p + i) = f2v{v[i], v[i + 1]};
+    else st1(i), st1(i + 1);
+  };
+  auto st4 = [&](int i) {
+    if (i >= lo && i + 4 <= hi) *reinterpret_cast<f4v*>(p + i) = f4v{v[i], v[i + 1], v[i + 2], v[i + 3]};
+    else st2(i), st2(i + 2);
+  };
+  if constexpr (A == 0) st4(0), st4(4);
+  else if constexpr (A == 2) st2(0), st4(2), st2(6);
+  else if constexpr (A == 1) st1(0), st2(1), st4(3), st1(7);
+  else st1(0), st4(1), st2(5), st1(7);
+}
+
+template <int CI, int CO, int RB, bool X2>
+__global__ __launch_bounds__(kBlock) void conv3d_t2_cells_kernel(
+    const float* __restrict__ x, const float* __restrict__ x2, const float* __restrict__ w,
+    float* __restrict__ y, const float* __restrict__ bn_scale, const float* __restrict__ bn_shift,
+    const float* __restrict__ bn_mean, Geo g) {
+  constexpr int NB = CO / 16, CB = CI / 16;
+  static_assert(CI % 16 == 0 && CO % 16 == 0, "channel counts in multiples of 16");
+  const int lane = (int)threadIdx.x & 63;
+  const int m = lane & 15, kq = lane >> 4;
+  const int b = (int)blockIdx.z;
+
+  // ---- cells: per dim every cell with an output in the region; row blocks of 16 cells along x ----
+  int cf[3], cn[3];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) cell_dim(g.o0[d], g.on[d], g.pad[d], cf[d], cn[d]);
+  const int nbx = (cn[2] + 15) >> 4;
+  const int blocks = cn[0] * cn[1] * nbx;
+  const int bx = xcd_work_id((int)blockIdx.x, (int)gridDim.x);
+  const int blk0 = uniform((bx * (kBlock / 64) + ((int)threadIdx.x >> 6)) * RB);
+  if (blk0 >= blocks) return;   // wave-uniform; no barriers in this kernel
+
+  // per row block (wave-uniform): its line and first cell; per lane: the linear index of cell m's input
+  // voxel c in the input region and, per dim, whether inputs c (bit 0) and c - 1 (bit 1) exist
+  const int sy = g.in[2], sz = g.in[1] * g.in[2];
+  bool live[RB];
+  int lz[RB], ly[RB], xb[RB], lin[RB];
+  unsigned vm[RB][3];
+#pragma unroll
+  for (int rb = 0; rb < RB; ++rb) {
+    live[rb] = blk0 + rb < blocks;
+    const int blk = live[rb] ? blk0 + rb : 0;
+    xb[rb] = blk % nbx;
+    const int line = blk / nbx;
+    ly[rb] = line % cn[1];
+    lz[rb] = line / cn[1];
+    const int ci[3] = {lz[rb], ly[rb], xb[rb] * 16 + m};   // cell index in the cell box
+    int bs[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      bs[d] = cf[d] + ci[d] - g.i0[d];
+      unsigned mk = 0;
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+        mk |= (live[rb] && ci[d] < cn[d] && bs[d] - j >= 0 && bs[d] - j < g.in[d]) ? (1u << j) : 0u;
+      vm[rb][d] = mk;
+    }
+    lin[rb] = (bs[0] * g.in[1] + bs[1]) * g.in[2] + bs[2];
+  }
+
+  f4v acc[8][RB][NB];
+#pragma unroll
+  for (int c = 0; c < 8; ++c)
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) acc[c][rb][nb] = f4v{0.0f, 0.0f, 0.0f, 0.0f};
+
+  // the sample's region tensor (and addend): out-of-range offsets read 0
+  const size_t rvol_in = (size_t)g.in[0] * g.in[1] * g.in[2];
+  const Rsrc rs = make_rsrc(x + (size_t)b * rvol_in * CI, (uint32_t)(rvol_in * CI * 4));
+  Rsrc rs2;
+  if constexpr (X2) rs2 = make_rsrc(x2 + (size_t)b * rvol_in * CI, (uint32_t)(rvol_in * CI * 4));
+
+  // ---- K loop: tap rows grouped by the input row they read ----
+  constexpr int kRowOrder[9][2] = {{0, 0}, {0, 1}, {1, 0}, {1, 1}, {0, 2}, {1, 2}, {2, 0}, {2, 1}, {2, 2}};
+  f4v a[RB][2][CB];   // the live input row: voxels x = c (0), c - 1 (1), all channel blocks
+#pragma unroll
+  for (int it = 0; it < 9; ++it) {
+    const int tz = kRowOrder[it][0], ty = kRowOrder[it][1];
+    const int jz = tz >> 1, jy = ty >> 1;
+    if (it == 0 || it == 4 || it == 6 || it == 8) {   // a new input row (jz, jy): each voxel loaded once
+#pragma unroll
+      for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+        for (int jx = 0; jx < 2; ++jx) {
+          const bool ok = ((vm[rb][0] >> jz) & (vm[rb][1] >> jy) & (vm[rb][2] >> jx) & 1u) != 0;
+          const uint32_t vo = (uint32_t)(lin[rb] - jz * sz - jy * sy - jx) * (uint32_t)(CI * 4) + (uint32_t)kq * 16u;
+#pragma unroll
+          for (int cb = 0; cb < CB; ++cb) {
+            const uint32_t eo = ok ? vo + (uint32_t)cb * 64u : kOob;
+            f4v v = ld4(rs, eo, 0);
+            if constexpr (X2) v += ld4(rs2, eo, 0);
+            a[rb][jx][cb] = v;
+          }
+        }
+    }
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb) {
+      const int c4 = cb * 16 + kq * 4;
+      f4v bw[3][NB];
+#pragma unroll
+      for (int tx = 0; tx < 3; ++tx) {
+        const float* wt = w + (size_t)((tz * 3 + ty) * 3 + tx) * CO * CI;
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb)
+          bw[tx][nb] = *reinterpret_cast<const f4v*>(wt + (size_t)(nb * 16 + m) * CI + c4);
+      }
+#pragma unroll
+      for (int tx = 0; tx < 3; ++tx) {
+        const int cls = ((tz & 1) << 2) | ((ty & 1) << 1) | (tx & 1);
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+          for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb)
+              acc[cls][rb][nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[rb][tx >> 1][cb][s], bw[tx][nb][s],
+                                                                      acc[cls][rb][nb], 0, 0, 0);
+      }
+    }
+  }
+
+  // ---- epilogue: eval BN + ReLU; acc[cls][rb][nb][r] = (cell 4 kq + r of the row block, channel nb * 16 + m),
+  // class (pz, py, px) = bits (2, 1, 0): output 2 c - P + par per dim, masked to the output region ----
+  const size_t rvol = (size_t)g.stn[0] * g.stn[1] * g.stn[2];
+#pragma unroll
+  for (int rb = 0; rb < RB; ++rb) {
+    // x of the lane's first output (cell 4 kq, px = 0) in the region; its run [lo, hi) of the 8
+    const int vx0 = 2 * (cf[2] + xb[rb] * 16 + kq * 4) - g.pad[2] - g.o0[2];
+    const int lo = vx0 < 0 ? -vx0 : 0, hi = g.on[2] - vx0 < 8 ? g.on[2] - vx0 : 8;
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) {
+      const int co = nb * 16 + m;
+      const float sc = bn_scale ? bn_scale[co] : 1.0f, sh = bn_scale ? bn_shift[co] : 0.0f,
+                  mu = bn_scale ? bn_mean[co] : 0.0f;
+#pragma unroll
+      for (int pzy = 0; pzy < 4; ++pzy) {
+        const int vz = 2 * (cf[0] + lz[rb]) + (pzy >> 1) - g.pad[0] - g.o0[0];
+        const int vy = 2 * (cf[1] + ly[rb]) + (pzy & 1) - g.pad[1] - g.o0[1];
+        if (!live[rb] || vz < 0 || vz >= g.on[0] || vy < 0 || vy >= g.on[1] || lo >= hi) continue;
+        float v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          float t = acc[pzy * 2 + (i & 1)][rb][nb][i >> 1];
+          if (bn_scale) t = fmaxf((t - mu) * sc + sh, 0.0f);
+          v[i] = t;
+        }
+        // element index of v[0] in the stored box (signed: v[0] may lie before the row's first voxel)
+        const long vox = ((long)(vz + g.st0[0]) * g.stn[1] + (vy + g.st0[1])) * g.stn[2] + (vx0 + g.st0[2]);
+        if (g.out_cf) {
+          const long e = (long)(((size_t)b * CO + co) * rvol) + vox;
+          float* p = y + e;
+          switch ((int)((reinterpret_cast<uintptr_t>(p) >> 2) & 3)) {
+            case 0: store_run8<0>(p, v, lo, hi); break;
+            case 1: store_run8<1>(p, v, lo, hi); break;
+            case 2: store_run8<2>(p, v, lo, hi); break;
+            default: store_run8<3>(p, v, lo, hi); break;
+          }
+        } else {
+          float* p = y + ((long)((size_t)b * rvol) + vox) * CO + co;
+#pragma unroll
+          for (int i = 0; i < 8; ++i)
+            if (i >= lo && i < hi) p[(long)i * CO] = v[i];
+        }
+      }
+    }
+  }
+}
+
+// 32 -> 16 (deconv_2_0): two row blocks per wave, 148 VGPRs with the addend / 160 without, no scratch, three
+// waves per SIMD (four row blocks: 240-248 VGPRs, two waves).  64 -> 32 (deconv_3_0) stays on the class
+// kernel: its region is small (25 x 17 x 21 cells at cfg 2) and a cell wave carries all 27 taps' weights
+// (27 x 4 x 2 float4 loads per 16 cells), so its few long waves are bound by their own load latency -- in
+// the cfg-2 eval step 0.226 ms (one row block, both column blocks per wave) and 0.260 ms (two row blocks,
+// the column blocks split over two waves) against the class kernel's 0.195 ms
+constexpr int kCellsRB = 2;
+
+template <int CI, int CO, int RB>
+void launch_t2_cells(const float* x, const float* x2, const float* w, float* y, const float* sc, const float* sh,
+                     const float* mu, int B, const Geo& g, hipStream_t s) {
+  const dim3 grid = cell_grid(RB, B, g.o0, g.on, g.pad);
+  if (x2)
+    hipLaunchKernelGGL((conv3d_t2_cells_kernel<CI, CO, RB, true>), grid, dim3(kBlock), 0, s, x, x2, w, y, sc, sh, mu, g);
+  else
+    hipLaunchKernelGGL((conv3d_t2_cells_kernel<CI, CO, RB, false>), grid, dim3(kBlock), 0, s, x, x2, w, y, sc, sh, mu, g);
+}
+
 // ---- stride-1 convolutions with LDS-staged operands (conv_k_1) ----
 // The per-lane kernel above fetches each input voxel once per tap through L1 / L2 (27 times) and keeps
 // at most RB row blocks of loads in flight: latency-bound (conv_1_1 at ~50 TF/s in the cfg-2 step).
@@ -541,18 +762,18 @@ int launch_conv3d_region(int mode, bool out_cf, int in_c4, const float* x, const
   // deconv_2_0 (32 -> 16)
   MVS_REGION_S2(32, 16) MVS_REGION_S2(32, 32) MVS_REGION_S2(32, 64)
   MVS_REGION_CASE(kS1, 16, 16) MVS_REGION_CASE(kS1, 32, 32) MVS_REGION_CASE(kS1, 64, 64)
-  // transposed: four row blocks per wave for deconv_2_0 (32 -> 16: 0.323 -> 0.302 ms at cfg 2), two for
-  // deconv_3_0 (64 -> 32: equal); MVS_T2_RB=2 / =4 forces one for both (A/B).  Per-output accumulation
-  // order does not depend on the row blocks: bit-equal either way
-  static const int t2_rb = [] {
-    const char* e = getenv("MVS_T2_RB");
-    return e && e[0] == '4' ? 4 : e && e[0] == '2' ? 2 : 0;
-  }();
-  if (mode == kT2 && CI == 64 && CO == 32 && t2_rb == 4)
-    return launch_mode<kT2, 64, 32, 4>(x, x2, w, y, bn_scale, bn_shift, bn_mean, B, g, s), MVS_OK;
-  if (mode == kT2 && CI == 32 && CO == 16 && t2_rb != 2)
+  // transposed 32 -> 16: the cell kernel (one pass per input cell, bit-equal to the class kernel; either
+  // layout, one or two inputs, any store box); the class kernel with per_lane (the autograd forward, tests),
+  // for 64 -> 32 (measured faster there, above), for an empty region, and with bound words: which of their
+  // slots a maximum lands in follows the class kernel's wave numbering (bound_update), and
+  // tests/golden/region_conv_pins.json pins those bytes; the fp32 eval chain asks for none
+  if (mode == kT2 && CI == 32 && CO == 16 && !per_lane && !y_bound && on[0] > 0 && on[1] > 0 && on[2] > 0)
+    return launch_t2_cells<32, 16, kCellsRB>(x, x2, w, y, bn_scale, bn_shift, bn_mean, B, g, s), MVS_OK;
+  // the class kernel: four row blocks per wave for deconv_2_0 (32 -> 16: 0.323 -> 0.302 ms at cfg 2), two
+  // for deconv_3_0 (64 -> 32: equal).  Per-output accumulation order does not depend on the row blocks
+  if (mode == kT2 && CI == 32 && CO == 16)
     return launch_mode<kT2, 32, 16, 4>(x, x2, w, y, bn_scale, bn_shift, bn_mean, B, g, s), MVS_OK;
-  MVS_REGION_CASE(kT2, 64, 32) MVS_REGION_CASE(kT2, 32, 16)
+  MVS_REGION_CASE(kT2, 64, 32)
 #undef MVS_REGION_CASE
 #undef MVS_REGION_S2
   return MVS_ERR_INVALID_ARGUMENT;

@@ -23,6 +23,14 @@ __device__ __forceinline__ void class_dim(int o0, int on, int p, int par, int& f
   cnt = first < o0 + on ? (o0 + on - 1 - first) / 2 + 1 : 0;
 }
 
+// T2 cells: output o belongs to cell (o + P) >> 1, which holds the outputs 2 c - P and 2 c - P + 1 (parity 0
+// and 1 of o + P) and reads the inputs c - 1 (tap 2, parity 0 only) and c (taps 0 / 1).  First cell with an
+// output in [o0, o0 + on) and the count of such cells; on >= 1
+__host__ __device__ __forceinline__ void cell_dim(int o0, int on, int p, int& first, int& cnt) {
+  first = (o0 + p) >> 1;
+  cnt = ((o0 + on - 1 + p) >> 1) - first + 1;
+}
+
 // ---- launch grids (multiples of the 8 XCDs: xcd_work_id) ----
 // the per-lane kernels: (row chunks of the largest parity class / of the region) x classes x batch
 inline dim3 region_grid(int mode, int RB, int B, const int* on) {
@@ -31,6 +39,15 @@ inline dim3 region_grid(int mode, int RB, int B, const int* on) {
                     (t2 ? (on[2] + 1) / 2 : on[2]);
   const long per_block = (kBlock / 64) * 16 * RB;
   return dim3(xcd_grid((int)((rows + per_block - 1) / per_block)).x, t2 ? 8u : 1u, (unsigned)B);
+}
+
+// the T2 cell kernel: (16-cell row blocks of every cell line, RB per wave) x batch
+inline dim3 cell_grid(int RB, int B, const int* o0, const int* on, const int* pad) {
+  int cf[3], cn[3];
+  for (int d = 0; d < 3; ++d) cell_dim(o0[d], on[d], pad[d], cf[d], cn[d]);
+  const long blocks = (long)cn[0] * cn[1] * ((cn[2] + 15) / 16);
+  const long waves = (blocks + RB - 1) / RB, per_block = kBlock / 64;
+  return dim3(xcd_grid((int)((waves + per_block - 1) / per_block)).x, 1u, (unsigned)B);
 }
 
 // the LDS-staged kernels: tiles x batch

@@ -507,7 +507,12 @@ int mvs_conv_head_fp32_fwd(const float* cv4, int batch, int d, int h, int w, con
  * summed in the order (tap, c_in) -- MIOpen sums them in other orders (fp32 rounding-level differences).
  * MVS_CONV_S1 with c_in = c_out and no x2 runs an LDS-staged kernel (each input voxel loaded once per
  * 16 x 4 x TZ output tile), bit-identical to the per-lane-operand kernel that flags MVS_CONV_PER_LANE
- * (below) selects. */
+ * (below) selects.  MVS_CONV_T2 (32, 16) runs the cell kernel (csrc/conv3d_region.hip conv3d_t2_cells_kernel: a GEMM
+ * row is a cell (o + pad) >> 1 per dim, whose 2 x 2 x 2 inputs are loaded once into registers and feed all
+ * eight output parity classes; no LDS; one or two inputs, either output layout), bit-identical to the
+ * parity-class kernel (one pass over the outputs per class, each class fetching its own taps' inputs), which
+ * MVS_CONV_PER_LANE selects and which also runs T2 (64, 32) (faster there: DESIGN.md section 3.3) and every
+ * call with y_bound (the words' slot assignment is that kernel's). */
 int mvs_conv3d_region_fwd(int mode, int flags, const float* x, const float* x2, const float* weight, float* y,
                           int batch, int c_in, int c_out, const int* dims, const int* out_origin,
                           const int* out_size, const int* in_origin, const int* in_size,
@@ -515,7 +520,8 @@ int mvs_conv3d_region_fwd(int mode, int flags, const float* x, const float* x2, 
                           const float* bn_mean, const unsigned* x_absmax, unsigned* y_bound, void* stream);
 
 /* flag of mvs_conv3d_region_split_fwd and mvs_conv3d_region_fwd: run the per-lane-operand kernel even
- * where an LDS-staged kernel applies (the two are bit-identical; tests and A/B timing) */
+ * where an LDS-staged kernel or (mvs_conv3d_region_fwd, MVS_CONV_T2 32 -> 16) the cell kernel applies (bit-identical;
+ * tests and A/B timing) */
 #define MVS_CONV_PER_LANE 32
 /* flag of mvs_conv3d_region_fwd: conv_1_0's shape (MVS_CONV_S2, c_in 32, c_out 16, the whole fp32 volume,
  * channel quads or NCDHW, channels-last output, no store box) on the LDS-staged kernel (csrc/conv3d_s2_lds.hip;
