@@ -18,19 +18,15 @@ to twenty times per site and keeps three or four full-size intermediates alive u
 
 The node also returns (scale, shift, mean) as differentiable per-channel outputs: bn_sums._bn_constant of them
 (relu(BN(0)), the next layer's border term) carries its gradient back through the same closed form."""
-import os
-
 import torch
 
 from .bn_sums import _bn_train
+from .train_switches import device_fp32, is_
 
 
 def enabled(x):
-    """MVS_TRAIN_BN, read on every call: "hip", or "torch" (the default, also when unset or empty; anything else
-    counts as "torch", as with the neighbouring switches).  A switch of its own: no other training switch turns
-    it on and it turns none of them on.  Applies to an fp32 device tensor under autograd."""
-    on = os.environ.get("MVS_TRAIN_BN", "torch") == "hip"
-    return on and x.is_cuda and x.dtype == torch.float32 and torch.is_grad_enabled()
+    """MVS_TRAIN_BN=hip (train_switches.TABLE), for an fp32 device tensor under autograd."""
+    return is_("MVS_TRAIN_BN", "hip") and device_fp32(x, grad=True)
 
 
 def _memory(t):

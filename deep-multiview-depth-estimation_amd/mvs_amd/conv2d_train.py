@@ -14,7 +14,7 @@ the layer keeps MIOpen's NCHW kernels.
 The two ops live in the namespace ``mvs_train``, registered when this module is first imported (model._run_stack
 imports it under the switch only): the ``mvs`` namespace is the drop-in surface and stays as it is.
 
-MVS_TRAIN_CONV2D_BWD (parsed in one place, model.conv2d_bwd_mode, once per _run_stack call): "hip", or "taps" (the
+MVS_TRAIN_CONV2D_BWD (train_switches.TABLE; read by model.conv2d_bwd_mode once per _run_stack call): "hip", or "taps" (the
 per-tap GEMMs; the default, also when unset or empty); anything else raises.  A switch of its own: no other switch
 enables it and it enables nothing else.  It acts only where tap_gemm.conv2d_hip_fwd acts (MVS_TRAIN_CONV2D=taps,
 MVS_TRAIN_CONV2D_FWD=hip, ops.conv2d_supported(layer), a 4-D fp32 HIP input), and only for the shapes in
@@ -29,7 +29,7 @@ from .ops import CONV2D_SHAPES, _conv2d_out, _require_gpu
 _F32 = torch.float32
 
 # (c_in, c_out, k, stride) whose HIP backward beats the per-tap GEMMs by more than the runs' spread at the cfg-2
-# sizes (tools/conv2d_bwd_layers.py, profiles/conv2d_bwd_layers_cfg2.txt); any other shape stays
+# sizes (tools/train_layer_ab.py --family conv2d, profiles/conv2d_bwd_layers_cfg2.txt); any other shape stays
 # on the GEMMs under "hip" too
 CONV2D_BWD_SHAPES = ((3, 8, 3, 1), (8, 8, 3, 1), (8, 16, 5, 2), (16, 16, 3, 1), (16, 32, 5, 2), (32, 32, 3, 1),
                      (4, 32, 3, 1), (32, 1, 3, 1))

@@ -31,7 +31,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import streams
+from . import streams, train_switches
 from .bn_sums import _bn_constant, _bn_train, _bn_train_hip, _border_class_sums, _border_tables_u  # noqa: F401
 from .config import MVSConfig
 from .costvolume import warp_and_assemble_cost_volume
@@ -60,11 +60,14 @@ def _conv_bn_relu_stack(spec, device):
 
 def conv2d_bwd_mode():
     """MVS_TRAIN_CONV2D_BWD, read once per _run_stack call: "hip" (mvs_amd/conv2d_train.py) or "taps" (the per-tap
-    GEMMs; the default, also when unset or empty); anything else raises.  A switch of its own."""
-    v = os.environ.get("MVS_TRAIN_CONV2D_BWD", "") or "taps"
-    if v not in ("hip", "taps"):
-        raise ValueError("MVS_TRAIN_CONV2D_BWD must be 'hip' or 'taps', got %r" % (v,))
-    return v
+    GEMMs; the default, also when unset or empty); anything else raises (train_switches.TABLE)."""
+    return train_switches.read("MVS_TRAIN_CONV2D_BWD")
+
+
+def conv2d_train_backends():
+    """(the Conv2d layers go through tap_gemm under autograd: MVS_TRAIN_CONV2D=taps, their forward on the HIP
+    kernel: MVS_TRAIN_CONV2D_FWD=hip), read once per _run_stack call."""
+    return train_switches.is_("MVS_TRAIN_CONV2D", "taps"), train_switches.is_("MVS_TRAIN_CONV2D_FWD", "hip")
 
 
 def _run_stack(seq, x, split_f16=False):
@@ -75,12 +78,12 @@ def _run_stack(seq, x, split_f16=False):
     with the running statistics updated as torch does.  Elsewhere the modules themselves.
     ``split_f16`` (MVSConfig(arithmetic="split_f16"), opt-in): the 8..32-channel layers on the f16
     matrix cores with split operands (csrc/conv2d_split.hip)."""
-    if _taps(x) and os.environ.get("MVS_TRAIN_CONV2D", "taps") == "taps":
+    taps, hip_fwd = conv2d_train_backends() if _taps(x) else (False, False)
+    if taps:
         # under autograd on a HIP device (train.py:97-104): the convolutions as per-tap rocBLAS GEMMs
         # (tap_gemm.conv2d), not MIOpen's (its first training step compiles its kernels: ~40 s at cfg 2)
         from . import tap_gemm
         from .ops import conv2d_supported
-        hip_fwd = os.environ.get("MVS_TRAIN_CONV2D_FWD", "hip") == "hip"
         # MVS_TRAIN_CONV2D_BWD=hip: both gradients on csrc/conv2d_bwd.hip too (conv2d_train.py; imported only then)
         hip_bwd = None
         if hip_fwd and conv2d_bwd_mode() == "hip":

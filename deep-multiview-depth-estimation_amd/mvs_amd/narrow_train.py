@@ -10,11 +10,10 @@ padding 1)) on the HIP kernels, fp32:
 They replace the per-tap rocBLAS GEMMs (tap_gemm.py), which stream the full volume once per tap in each
 pass (cfg 2: 112 ms for conv_0_0's forward + backward, 106 ms for conv_out's; the per-layer
 tool that measured it is no longer in the tree)."""
-import os
-
 import torch
 
 from . import ops
+from .train_switches import device_fp32, is_
 
 
 def applies(conv, x):
@@ -22,7 +21,7 @@ def applies(conv, x):
     kernel 3, stride 1, padding 1, no bias, (c_in, c_out) with a weight-gradient kernel
     (ops.WGRAD_SHAPES), MVS_TRAIN_NARROW not 0."""
     w = conv.weight
-    return (os.environ.get("MVS_TRAIN_NARROW", "1") != "0" and x.is_cuda and x.dtype == torch.float32
+    return (not is_("MVS_TRAIN_NARROW", "0") and device_fp32(x)
             and x.dim() == 5 and not torch.is_autocast_enabled() and conv.bias is None and conv.groups == 1
             and tuple(w.shape[2:]) == (3, 3, 3) and tuple(conv.stride) == (1, 1, 1)
             and tuple(conv.padding) == (1, 1, 1) and tuple(conv.dilation) == (1, 1, 1)

@@ -8,50 +8,101 @@ conv3d_box / conv_transpose3d_box).  The tap GEMMs accumulate every tap's produc
   stride-2 conv_k_0 (model.py:101-107, stacked 32 -> 16 + 32 + 64 over R2)  mode S2, one launch per layer
   stride-1 conv_k_1 (model.py:108-113, on R1 from the padded R2 crop)         mode S1
   transposed deconv_3_0 / deconv_2_0 (model.py:117-120, the full box from M)  mode T2
-MVS_TRAIN_REGION_FWD selects which (enabled()).  MVS_TRAIN_REGION_BWD (bwd_enabled(), default "taps") moves
-the stride-1 layers' backward onto HIP kernels as well: the input gradient on the forward's region kernel
-in its adjoint geometry, the weight gradient on csrc/conv3d_region_wgrad.hip.  MVS_TRAIN_S2_BWD
-(s2_bwd_enabled(), default "taps") does the same for the stacked stride-2 layer: the input gradient on the
-region kernel's transposed mode, the weight gradient on csrc/conv3d_s2_wgrad.hip, both from the NCDHW volume
-in place.  MVS_TRAIN_T2_BWD (t2_bwd_enabled(), default "taps") does it for deconv_3_0 / deconv_2_0: the input
-gradient on the region kernel's stride-2 mode with the channels-last output gradient as the volume, the weight
-gradient on csrc/conv3d_t2_wgrad.hip.  deconv_1_0 (16 -> 8, the full-size output, dims=None in _tconv_region)
-comes under none of these: MVS_TRAIN_DECONV1 (d1_enabled(), default "taps") moves it onto HIP kernels in both
-directions at once -- the forward on csrc/deconv3d_region.hip in raw mode (one pass instead of 27 tap passes over
-the output), the input and weight gradients on csrc/deconv3d_region_bwd.hip, reading the NCDHW output gradient in
-place and x in the channels-last memory it arrives in."""
-import os
-
+Which layer runs where is decided once per layer by s2_route / s1_route / tconv_route below, from the training
+switches (train_switches.TABLE lists them: what each moves, its words and its default)."""
 import torch
 
 from . import tap_gemm
 from .regions import extent, origin
+from .train_switches import device_fp32, is_, names
 
 S2_SPLITS = (16, 32, 64)   # conv_1_0, conv_2_0, conv_3_0 output channels (the stacked S2 order)
 S1_CHANNELS = (16, 32, 64)
 T2_SHAPES = ((64, 32), (32, 16))   # (c_in, c_out) of deconv_3_0, deconv_2_0
-
-
-def enabled(x, kind=None):
-    """kind "s2" / "s1" / "t2"; MVS_TRAIN_REGION_FWD: a comma list of kinds (default "s1,t2"), "hip" (all)
-    or "taps" (none).  The stride-2 forward stays on the tap GEMMs by default: with it on the HIP kernel
-    test_gpu_train.py::test_train_mode_autograd_chain_smooth_loss's deconv_1_0 weight gradient lands 2.8x
-    the CPU fp32 error from float64 (0.0074 against 0.0027)."""
-    v = os.environ.get("MVS_TRAIN_REGION_FWD", "s1,t2")
-    on = v == "hip" or (kind is not None and kind in v.split(","))
-    return on and x.is_cuda and x.dtype == torch.float32 and torch.is_grad_enabled()
-
-
-BWD_KINDS = ("s1",)               # kinds with a HIP backward
+D1_SHAPE = (16, 8)                 # (c_in, c_out) of deconv_1_0
+BWD_KINDS = ("s1",)               # kinds with a HIP backward under MVS_TRAIN_REGION_BWD
 S1_BWD_CHANNELS = (16, 32, 64)    # channel counts of "s1" whose HIP backward beats the tap GEMMs (DESIGN.md §3.6)
 
 
+# The switches as predicates (train_switches.TABLE documents each).
+
+def enabled(x, kind=None):
+    """The forward of ``kind`` ("s2" / "s1" / "t2") runs on the HIP region kernel: MVS_TRAIN_REGION_FWD."""
+    return names("MVS_TRAIN_REGION_FWD", kind) and device_fp32(x, grad=True)
+
+
 def bwd_enabled(kind, channels=None):
-    """The backward of ``kind`` runs on the HIP kernels.  MVS_TRAIN_REGION_BWD, read on every call: a comma
-    list of kinds, "hip" (every kind in BWD_KINDS) or "taps" (none: the per-tap GEMMs; the default)."""
-    v = os.environ.get("MVS_TRAIN_REGION_BWD", "taps")
-    on = kind in BWD_KINDS and (v == "hip" or kind in v.split(","))
+    """The backward of ``kind`` runs on the HIP kernels: MVS_TRAIN_REGION_BWD, for the kinds in BWD_KINDS."""
+    on = kind in BWD_KINDS and names("MVS_TRAIN_REGION_BWD", kind)
     return on and (kind != "s1" or channels is None or channels in S1_BWD_CHANNELS)
+
+
+def s2_bwd_enabled(x):
+    """The stacked stride-2 layers' backward runs on ops.conv3d_s2_region_wgrad / _dgrad: MVS_TRAIN_S2_BWD."""
+    return is_("MVS_TRAIN_S2_BWD", "hip") and device_fp32(x)
+
+
+def t2_bwd_enabled(x):
+    """deconv_3_0 / deconv_2_0's backward runs on ops.conv3d_t2_region_wgrad / _dgrad: MVS_TRAIN_T2_BWD."""
+    return is_("MVS_TRAIN_T2_BWD", "hip") and device_fp32(x)
+
+
+def d1_enabled(x):
+    """deconv_1_0 runs forward and backward on ops.deconv3d_k3s2 / _wgrad / _dgrad: MVS_TRAIN_DECONV1."""
+    return is_("MVS_TRAIN_DECONV1", "hip") and device_fp32(x)
+
+
+def d1_applies(x, w):
+    """d1_enabled for a tensor under autograd and the (16, 8) weight."""
+    return d1_enabled(x) and torch.is_grad_enabled() and tuple(w.shape) == D1_SHAPE + (3, 3, 3)
+
+
+# One routing decision per layer family, asked once by regions.py (inside its own "under autograd on a HIP device
+# in fp32" branch): None = stay on the tap GEMMs, else the (HIP forward?, HIP backward?) pair the autograd box is
+# applied with.
+
+def s2_route(x, w, whole, splits, direct=False):
+    """The stride-2 layer on its output box.  ``whole``: the box reads the whole volume (no crop); ``splits``: the
+    output channels of the layers stacked in ``w``.  The layer goes to _S2Box when either MVS_TRAIN_REGION_FWD
+    names "s2" or MVS_TRAIN_S2_BWD is "hip".  ``direct`` (s2_box called without a route, as tests do): no gate."""
+    fwd, bwd = enabled(x, "s2"), s2_bwd_enabled(x)
+    if not direct and not (whole and splits is not None and x.shape[1] == 32
+                           and tuple(splits) in (S2_SPLITS, (16,), (32,), (64,)) and (fwd or bwd)):
+        return None
+    # the forward is the tap GEMMs' when only MVS_TRAIN_S2_BWD brought the layer here; with neither switch (a direct
+    # call only) it stays the HIP kernel.  The HIP backward exists for the stacked (16, 32, 64) split of 32 input
+    # channels only.
+    return fwd or not bwd, bwd and x.shape[1] == 32 and tuple(splits) == S2_SPLITS
+
+
+def s1_backward(w):
+    """The HIP backward of a stride-1 layer: MVS_TRAIN_REGION_BWD names "s1" and c_out is in S1_BWD_CHANNELS."""
+    return bwd_enabled("s1", w.shape[0])
+
+
+def s1_route(x, w):
+    """The stride-1 layer on its padded crop: the HIP forward (_S1Valid) for the square S1_CHANNELS weights when
+    MVS_TRAIN_REGION_FWD names "s1"; the backward as s1_backward says."""
+    if not (enabled(x, "s1") and w.shape[0] == w.shape[1] and w.shape[0] in S1_CHANNELS):
+        return None
+    return True, s1_backward(w)
+
+
+def t2_backward(x, w):
+    """The HIP backward of a transposed layer: MVS_TRAIN_T2_BWD=hip and a (c_in, c_out) in T2_SHAPES."""
+    return t2_bwd_enabled(x) and (w.shape[0], w.shape[1]) in T2_SHAPES
+
+
+def tconv_route(x, w, no_dims):
+    """The transposed layers.  With the volume extent given (``no_dims`` False: deconv_3_0 / deconv_2_0) the HIP
+    forward (_T2Box) for T2_SHAPES when MVS_TRAIN_REGION_FWD names "t2", the backward as t2_backward says.  Without
+    it (deconv_1_0, whose output is the full-size volume) both directions on HIP (_D1Box) when d1_applies: D1_SHAPE
+    under MVS_TRAIN_DECONV1=hip.  No other switch moves deconv_1_0, and MVS_TRAIN_DECONV1 moves nothing else."""
+    if no_dims:
+        return (True, True) if d1_applies(x, w) else None
+    if enabled(x, "t2") and (w.shape[0], w.shape[1]) in T2_SHAPES:
+        return True, t2_backward(x, w)
+    return None
 
 
 def _region_w(w):      # Conv3d weight [co, ci, 3, 3, 3] -> [27][co][ci]
@@ -64,14 +115,6 @@ def _region_wt(w):     # ConvTranspose3d weight [ci, co, 3, 3, 3] -> [27][co][ci
 
 def _cf(t):            # channels-last [B, d, h, w, C] -> logical NCDHW view
     return t.permute(0, 4, 1, 2, 3)
-
-
-def s2_bwd_enabled(x):
-    """The backward of the stacked stride-2 layers (32 -> 16 + 32 + 64) runs on the HIP kernels
-    (ops.conv3d_s2_region_wgrad / conv3d_s2_region_dgrad).  MVS_TRAIN_S2_BWD, read on every call: "hip", or
-    "taps" (the per-tap GEMMs; the default).  A switch of its own: MVS_TRAIN_REGION_BWD never names "s2"."""
-    on = os.environ.get("MVS_TRAIN_S2_BWD", "taps") == "hip"
-    return on and x.is_cuda and x.dtype == torch.float32
 
 
 class _S2Box(torch.autograd.Function):
@@ -124,20 +167,20 @@ def _region_w_adjoint(w):   # Conv3d weight [co, ci, 3, 3, 3] -> the input gradi
 
 class _S1Valid(torch.autograd.Function):
     """conv3d(xin, w) with padding 0 (xin: the zero-padded crop of _conv_s1_region).  With the HIP backward
-    (bwd_enabled("s1", C)) the channels-last copy the forward makes anyway is what is saved, and the backward is
+    (hip_bwd, decided by the caller) the channels-last copy the forward makes anyway is what is saved, and the backward is
       d/dw  gw[co][ci][t] = sum gy[o][co] x[o + t][ci]                 ops.conv3d_region_wgrad
       d/dx  gx[i] = sum_t gy[i - t] w[.][.][t] = conv(gy, w~) on the box of xin, gy zero outside its own:
             the forward's region kernel with gy as the input region at origin 1 of a volume of xin's
             extent, w~[t][ci][co] = w[co][ci][2 - t] per dim."""
 
     @staticmethod
-    def forward(ctx, xin, w):
+    def forward(ctx, xin, w, hip_bwd):
         from .ops import CONV_S1, conv3d_region
         L = list(xin.shape[2:])
         out = [d - 2 for d in L]
         x_cl = xin.permute(0, 2, 3, 4, 1).contiguous()
         y = conv3d_region(x_cl, None, _region_w(w), CONV_S1, L, [1, 1, 1], out, [0, 0, 0], L, None)
-        ctx.hip_bwd = bwd_enabled("s1", w.shape[0])
+        ctx.hip_bwd = hip_bwd
         ctx.save_for_backward(x_cl if ctx.hip_bwd else xin, w)
         ctx.out = tuple(out)
         return _cf(y)
@@ -147,7 +190,7 @@ class _S1Valid(torch.autograd.Function):
         xin, w = ctx.saved_tensors
         if not ctx.hip_bwd:
             return tap_gemm.conv3d_backward(xin, w, 1, 0, ctx.out, gy, ctx.needs_input_grad[0],
-                                            ctx.needs_input_grad[1])
+                                            ctx.needs_input_grad[1]) + (None,)
         from .ops import CONV_S1, conv3d_region, conv3d_region_wgrad
         gy_cl = gy.permute(0, 2, 3, 4, 1).contiguous()
         gx = gw = None
@@ -157,15 +200,7 @@ class _S1Valid(torch.autograd.Function):
                                    list(ctx.out), None, per_lane=True))
         if ctx.needs_input_grad[1]:
             gw = conv3d_region_wgrad(xin, gy_cl)
-        return gx, gw
-
-
-def t2_bwd_enabled(x):
-    """The backward of the transposed region convolutions deconv_3_0 / deconv_2_0 (T2_SHAPES) runs on the HIP
-    kernels (ops.conv3d_t2_region_wgrad / conv3d_t2_region_dgrad).  MVS_TRAIN_T2_BWD, read on every call: "hip",
-    or "taps" (the per-tap GEMMs; the default).  A switch of its own: MVS_TRAIN_REGION_BWD never names "t2"."""
-    on = os.environ.get("MVS_TRAIN_T2_BWD", "taps") == "hip"
-    return on and x.is_cuda and x.dtype == torch.float32
+        return gx, gw, None
 
 
 class _T2Box(torch.autograd.Function):
@@ -201,18 +236,6 @@ class _T2Box(torch.autograd.Function):
         return gx, gw, None, None, None, None, None, None
 
 
-D1_SHAPE = (16, 8)   # (c_in, c_out) of deconv_1_0
-
-
-def d1_enabled(x):
-    """deconv_1_0 (D1_SHAPE, the transposed layer whose output is the full-size volume) runs forward and backward
-    on the HIP kernels under autograd (ops.deconv3d_k3s2 / deconv3d_k3s2_wgrad / deconv3d_k3s2_dgrad).
-    MVS_TRAIN_DECONV1, read on every call: "hip", or "taps" (the per-tap GEMMs; the default, also when unset or
-    empty).  A switch of its own: no other switch enables it and it enables nothing else."""
-    on = os.environ.get("MVS_TRAIN_DECONV1", "taps") == "hip"
-    return on and x.is_cuda and x.dtype == torch.float32
-
-
 class _D1Box(torch.autograd.Function):
     """deconv_1_0 on its output box: the forward on csrc/deconv3d_region.hip in raw mode (no BN, no residual; one
     pass, y NCDHW), the backward on csrc/deconv3d_region_bwd.hip, reading gy NCDHW in place and returning gx in
@@ -240,32 +263,24 @@ class _D1Box(torch.autograd.Function):
         return gx, gw, None, None, None
 
 
-def d1_applies(x, w):
-    """_tconv_region sends the layer to d1_box: the switch on, a GPU fp32 tensor under autograd, the (16, 8) weight."""
-    return d1_enabled(x) and torch.is_grad_enabled() and tuple(w.shape) == D1_SHAPE + (3, 3, 3)
-
+# The boxes' entry points.  regions.py passes the route it asked for; a call without one (tests, tools) asks here.
+# Either way the backends are fixed before apply (grad mode is off inside forward).
 
 def d1_box(x, w, out_reg, crop):
-    """deconv_1_0 under MVS_TRAIN_DECONV1=hip (d1_applies).  Which memory layout the kernels read x in (and return
-    gx in) is decided here, before apply: channels-last in place when x's memory is, else NCDHW."""
+    """deconv_1_0 where tconv_route sent it.  Which memory layout the kernels read x in (and return gx in) is
+    decided here: channels-last in place when x's memory is, else NCDHW."""
     from .ops import _is_cl5
     return _D1Box.apply(x, w, tuple(crop), tuple(extent(out_reg)), _is_cl5(x))
 
 
-def s2_box(x, w, out_reg, pad, pad_lo, splits):
-    """Forward and backward kind are decided here, before apply.  _conv_s2_region comes here when either
-    switch is on: the forward is the HIP kernel when MVS_TRAIN_REGION_FWD names "s2", and the tap GEMMs when
-    only MVS_TRAIN_S2_BWD brought the layer here (a direct call with neither switch keeps the HIP forward)."""
-    hip_bwd = s2_bwd_enabled(x) and x.shape[1] == 32 and tuple(splits) == S2_SPLITS
-    return _S2Box.apply(x, w, out_reg, pad, pad_lo, splits, enabled(x, "s2") or not s2_bwd_enabled(x), hip_bwd)
+def s2_box(x, w, out_reg, pad, pad_lo, splits, route=None):
+    hip_fwd, hip_bwd = route or s2_route(x, w, True, splits, direct=True)
+    return _S2Box.apply(x, w, out_reg, pad, pad_lo, splits, hip_fwd, hip_bwd)
 
 
-def s1_valid(xin, w):
-    return _S1Valid.apply(xin, w)
+def s1_valid(xin, w, route=None):
+    return _S1Valid.apply(xin, w, route[1] if route else s1_backward(w))
 
 
-def t2_box(x, w, x_reg, out_reg, pad, dims, crop):
-    """The backward kind is decided here, before apply (deconv_1_0, 16 -> 8 with dims=None, never comes here:
-    it goes to d1_box under MVS_TRAIN_DECONV1=hip and to the tap GEMMs otherwise)."""
-    hip_bwd = t2_bwd_enabled(x) and (w.shape[0], w.shape[1]) in T2_SHAPES
-    return _T2Box.apply(x, w, x_reg, out_reg, pad, dims, crop, hip_bwd)
+def t2_box(x, w, x_reg, out_reg, pad, dims, crop, route=None):
+    return _T2Box.apply(x, w, x_reg, out_reg, pad, dims, crop, route[1] if route else t2_backward(x, w))

@@ -97,10 +97,9 @@ def _conv_s2_region(x, weight, out_reg, pad, splits=None):
             pl.append(ca - a)
         whole = all(s_.start == 0 and s_.stop == d for s_, d in zip(sl, n))
         from . import region_train
-        if (whole and splits is not None and x.shape[1] == 32
-                and tuple(splits) in (region_train.S2_SPLITS, (16,), (32,), (64,))
-                and (region_train.enabled(x, "s2") or region_train.s2_bwd_enabled(x))):
-            return region_train.s2_box(x, weight, out_reg, pad, tuple(pl), tuple(splits))   # HIP forward / backward
+        route = region_train.s2_route(x, weight, whole, splits)
+        if route is not None:
+            return region_train.s2_box(x, weight, out_reg, pad, tuple(pl), tuple(splits), route)
         if not whole:   # (a whole-extent slice: no copy back in the backward)
             x = x[:, :, sl[0], sl[1], sl[2]]
         return tap_gemm.conv3d_box(x, weight, 2, tuple(pl), tuple(extent(out_reg)))
@@ -126,9 +125,9 @@ def _conv_s1_region(x, x_reg, weight, out_reg, n):
     want = tuple((lo - 1, hi + 1) for lo, hi in out_reg)
     xin = _crop_pad(x, x_reg, want, n)
     from . import region_train
-    if (_taps(x) and region_train.enabled(x, "s1") and weight.shape[0] == weight.shape[1]
-            and weight.shape[0] in region_train.S1_CHANNELS):
-        return region_train.s1_valid(xin, weight)   # HIP forward, per-tap-GEMM backward
+    route = region_train.s1_route(x, weight) if _taps(x) else None
+    if route is not None:
+        return region_train.s1_valid(xin, weight, route)
     return _region_conv3d(xin, weight, 1, 0)
 
 
@@ -143,11 +142,11 @@ def _tconv_region(x, x_reg, weight, out_reg, pad, dims=None):
             assert lo - (2 * xlo - p) >= 0, "transposed-conv input region starts after the output box"
             crop.append(lo - (2 * xlo - p))
         from . import region_train
-        if (dims is not None and region_train.enabled(x, "t2")
-                and (weight.shape[0], weight.shape[1]) in region_train.T2_SHAPES):
-            return region_train.t2_box(x, weight, x_reg, out_reg, pad, dims, tuple(crop))   # HIP forward
-        if dims is None and region_train.d1_applies(x, weight):
+        route = region_train.tconv_route(x, weight, dims is None)
+        if route is not None and dims is None:
             return region_train.d1_box(x, weight, out_reg, tuple(crop))   # deconv_1_0: HIP forward and backward
+        if route is not None:
+            return region_train.t2_box(x, weight, x_reg, out_reg, pad, dims, tuple(crop), route)
         return tap_gemm.conv_transpose3d_box(x, weight, 2, tuple(crop), tuple(extent(out_reg)))
     y = F.conv_transpose3d(x, weight, stride=2)   # output q <-> volume index 2 * xlo + q - P
     sl, pads = [], []

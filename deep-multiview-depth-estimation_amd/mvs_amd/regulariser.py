@@ -11,6 +11,7 @@ from . import streams
 from .bn_sums import _apply_bn, _bn_constant, _bn_train, _bn_train_hip, _border_class_sums, _sums
 from .regions import (_conv_s1_region, _conv_s2_region, _crop_cf, _crop_cl, _crop_pad, _grow, _tconv_region,
                       extent, live_regions, origin)
+from .train_switches import device_fp32, is_
 
 
 def _bn_eval(bn):
@@ -118,9 +119,9 @@ class CostVolumeReg(nn.Module):
         the stride-2 convs and the deeper levels on 1/8 .. 1/512 of the volume).  On a HIP device in fp32,
         train-mode BN with running statistics, the module's padding derived from the volume extent;
         MVS_TRAIN_LIVE=0 keeps forward_full."""
-        return (self.live_region and torch.is_grad_enabled() and cv.is_cuda and cv.dtype == torch.float32
+        return (self.live_region and device_fp32(cv, grad=True)
                 and cv.dim() == 5 and not torch.is_autocast_enabled()
-                and os.environ.get("MVS_TRAIN_LIVE", "1") != "0" and self._live_geometry_ok(tuple(cv.shape[2:]))
+                and not is_("MVS_TRAIN_LIVE", "0") and self._live_geometry_ok(tuple(cv.shape[2:]))
                 and self._bn_batch_stats_ready())
 
     def head_ok(self, dcv):

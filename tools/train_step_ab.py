@@ -1,8 +1,9 @@
 """cfg-2 train.py step (bench.train_step_bench) on the live-region regulariser under autograd
-(default) or forward_full (--full: MVS_TRAIN_LIVE=0), with a per-kernel summary from the torch
-profiler of one step (--prof).
+(default) or forward_full (--full: MVS_TRAIN_LIVE=0), under an assignment of the training switches
+(--switches: a preset of mvs_amd/train_switches.py, "default" or "all_hip", or NAME=value,NAME=value; printed
+in the JSON line as "switches"), with a per-kernel summary from the torch profiler of one step (--prof).
 
-Usage: python tools/train_step_ab.py [--full] [--steps N] [--prof]"""
+Usage: python tools/train_step_ab.py [--switches all_hip] [--full] [--steps N] [--prof]"""
 import argparse
 import json
 import os
@@ -18,13 +19,20 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--prof", action="store_true")
     ap.add_argument("--ops", action="store_true", help="with --prof: aten ops grouped by input shape")
+    ap.add_argument("--switches", default="default", metavar="PRESET_OR_ASSIGNMENTS",
+                    help="a preset of mvs_amd/train_switches.py (default, all_hip) or NAME=value,NAME=value")
     a = ap.parse_args()
+    sys.path.insert(0, os.path.join(REPO, "deep-multiview-depth-estimation_amd"))
+    from mvs_amd import train_switches
+    assignment = train_switches.parse_assignment(a.switches)
     if a.full:
-        os.environ["MVS_TRAIN_LIVE"] = "0"
+        assignment["MVS_TRAIN_LIVE"] = "0"
+    os.environ.update(assignment)   # before bench is imported
     import bench
     import torch
     dev = torch.device("cuda", 0)
     out = bench.train_step_bench(4, 3, 192, 512, 640, dev, a.steps)
+    out["switches"] = assignment
     print(json.dumps(out), flush=True)
     if a.prof:
         from torch.profiler import ProfilerActivity, profile
