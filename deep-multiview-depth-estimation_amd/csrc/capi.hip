@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "../../include/train/mvs_loss.h"
 #include "../../include/train/mvs_region_train.h"
 #include "launchers.h"
 
@@ -1184,6 +1185,61 @@ int mvs_bn_relu_bwd_apply(const float* z, const float* gy, int layout, int batch
   const mvs::LaunchCheck lc;
   mvs::launch_bn_relu_bwd_apply(z, gy, (layout & MVS_LAYOUT_CHANNELS_LAST) != 0, batch, channels, dims, o, s, scale,
                                 shift, mean, g_s1, g_s2, gz, (hipStream_t)stream);
+  return lc.status();
+}
+
+// ---- training extension: the objective and the depth accuracy (loss.hip; include/train/mvs_loss.h) ----
+namespace {
+// MVS_OK when the mvs_masked_mae_* launches can run on these dimensions
+int masked_mae_geometry(int batch, int h, int w) {
+  if (batch <= 0 || h <= 0 || w <= 0) return MVS_ERR_INVALID_ARGUMENT;
+  if ((uint64_t)h * (uint64_t)w >= (1ull << 31) || batch > 65535) return MVS_ERR_TOO_LARGE;   // counts; grid.y
+  return MVS_OK;
+}
+}  // namespace
+
+int mvs_masked_mae_plan(int batch, int h, int w, int* workgroups, int* passes) {
+  const int st = masked_mae_geometry(batch, h, w);
+  if (st != MVS_OK) return st;
+  const mvs::MaskedMaePlan p = mvs::masked_mae_plan(batch, (size_t)h * (size_t)w);
+  if (workgroups) *workgroups = p.workgroups;
+  if (passes) *passes = p.passes;
+  return MVS_OK;
+}
+
+size_t mvs_masked_mae_workspace_bytes(int batch, int h, int w) {
+  if (masked_mae_geometry(batch, h, w) != MVS_OK) return 0;
+  return (size_t)mvs::masked_mae_plan(batch, (size_t)h * (size_t)w).workgroups * (size_t)batch * 5 * 8;
+}
+
+int mvs_masked_mae_fwd(const float* gt, const float* initial, const float* refined, int batch, int h, int w,
+                       float thresh, float* loss0, float* loss1, float* acc0, float* acc1, float* n_valid,
+                       void* workspace, void* stream) {
+  if (!gt || !initial || !refined || !loss0 || !loss1 || !acc0 || !acc1 || !n_valid || !workspace)
+    return MVS_ERR_INVALID_ARGUMENT;
+  if (((uintptr_t)gt | (uintptr_t)initial | (uintptr_t)refined | (uintptr_t)loss0 | (uintptr_t)loss1 |
+       (uintptr_t)acc0 | (uintptr_t)acc1 | (uintptr_t)n_valid) & 3u || (uintptr_t)workspace & 7u)
+    return MVS_ERR_INVALID_ARGUMENT;
+  if (!(thresh >= 0.0f)) return MVS_ERR_INVALID_ARGUMENT;   // (negative or NaN)
+  const int st = masked_mae_geometry(batch, h, w);
+  if (st != MVS_OK) return st;
+  const mvs::LaunchCheck lc;
+  mvs::launch_masked_mae_fwd(gt, initial, refined, batch, (size_t)h * (size_t)w, thresh, loss0, loss1, acc0, acc1,
+                             n_valid, static_cast<unsigned long long*>(workspace), (hipStream_t)stream);
+  return lc.status();
+}
+
+int mvs_masked_mae_bwd(const float* gt, const float* initial, const float* refined, const float* c0, const float* c1,
+                       int batch, int h, int w, float* g_initial, float* g_refined, void* stream) {
+  if (!gt || !initial || !refined || !c0 || !c1 || !g_initial || !g_refined) return MVS_ERR_INVALID_ARGUMENT;
+  if (((uintptr_t)gt | (uintptr_t)initial | (uintptr_t)refined | (uintptr_t)c0 | (uintptr_t)c1 |
+       (uintptr_t)g_initial | (uintptr_t)g_refined) & 3u)
+    return MVS_ERR_INVALID_ARGUMENT;
+  const int st = masked_mae_geometry(batch, h, w);
+  if (st != MVS_OK) return st;
+  const mvs::LaunchCheck lc;
+  mvs::launch_masked_mae_bwd(gt, initial, refined, c0, c1, batch, (size_t)h * (size_t)w, g_initial, g_refined,
+                             (hipStream_t)stream);
   return lc.status();
 }
 

@@ -247,6 +247,20 @@ void launch_bn_relu_bwd_apply(const float* z, const float* gy, bool channels_las
                               const int* o, const int* s, const float* sc, const float* sh, const float* mu,
                               const float* gs1, const float* gs2, float* gz, hipStream_t st);
 
+// loss.hip: loss.py's masked mean absolute error and the depth accuracy of gt / initial / refined [B][n]
+// (mvs_masked_mae_*).  The plan: workgroups per sample (the grid is workgroups x B; = the slots of the forward) and
+// the grid-stride passes each makes over a sample's ceil(n / 4) four-element items.  fwd: ws[workgroups][B][5]
+// 8-byte words, every one written once, then the five [B] fp32 results; bwd: both gradients, every element written
+struct MaskedMaePlan {
+  int workgroups, passes;
+};
+MaskedMaePlan masked_mae_plan(int B, size_t n);
+void launch_masked_mae_fwd(const float* gt, const float* x0, const float* x1, int B, size_t n, float thresh,
+                           float* loss0, float* loss1, float* acc0, float* acc1, float* n_valid,
+                           unsigned long long* ws, hipStream_t st);
+void launch_masked_mae_bwd(const float* gt, const float* x0, const float* x1, const float* c0, const float* c1, int B,
+                           size_t n, float* g0, float* g1, hipStream_t st);
+
 // dtu_input.hip: data.py:206-210 image normalisation (uint8 HWC -> fp32 NCHW), data.py:300-301
 // depth thresholds
 void launch_normalize_images(const uint8_t* rgb, int n, uint32_t hw, const float* mean3,

@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI in ``include/mvs_cost_volume.h`` and of its training extension
-``include/train/mvs_region_train.h`` (libmvs_cost_volume.so).
+``include/train/mvs_region_train.h`` and ``include/train/mvs_loss.h`` (libmvs_cost_volume.so).
 
 The library is built in-tree by ``mvs_amd._build.build_library()`` (called from
 ``__graft_entry__.build()``) and travels to the GPU box as a file next to this module.  There is
@@ -130,6 +130,15 @@ TRAIN_SIGNATURES = {
     "mvs_conv2d_dgrad": (_c_int, [_p, _p] + [_c_int] * 7 + [_p, _p]),
 }
 
+# the objective and the depth accuracy (include/train/mvs_loss.h): part of the training extension, a header and
+# a table of its own (TRAIN_SIGNATURES is mvs_region_train.h's, name for name)
+LOSS_SIGNATURES = {
+    "mvs_masked_mae_plan": (_c_int, [_c_int, _c_int, _c_int, _p, _p]),
+    "mvs_masked_mae_workspace_bytes": (ctypes.c_size_t, [_c_int, _c_int, _c_int]),
+    "mvs_masked_mae_fwd": (_c_int, [_p, _p, _p, _c_int, _c_int, _c_int, _c_float] + [_p] * 7),
+    "mvs_masked_mae_bwd": (_c_int, [_p] * 5 + [_c_int] * 3 + [_p] * 3),
+}
+
 
 class MVSLibraryError(RuntimeError):
     """The HIP library is missing, stale, or a kernel call failed."""
@@ -148,7 +157,7 @@ def load():
             "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950); there is no CPU fallback" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for table in (SIGNATURES, TRAIN_SIGNATURES):
+    for table in (SIGNATURES, TRAIN_SIGNATURES, LOSS_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)
             fn.restype = res
