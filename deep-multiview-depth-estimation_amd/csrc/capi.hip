@@ -986,8 +986,9 @@ int mvs_conv3d_region_split_fwd(int mode, int flags, const float* x, const float
           store_origin[k] + store_size[k] > out_origin[k] + out_size[k])
         return MVS_ERR_INVALID_ARGUMENT;
   if (mode < MVS_CONV_S1 || mode > MVS_CONV_T2 ||
-      (flags & ~(MVS_CONV_OUT_NCDHW | MVS_CONV_IN_C4 | MVS_CONV_IN_SPLIT | MVS_CONV_PER_LANE)))
+      (flags & ~(MVS_CONV_OUT_NCDHW | MVS_CONV_IN_C4 | MVS_CONV_IN_SPLIT | MVS_CONV_PER_LANE | MVS_CONV_T2_LDS)))
     return MVS_ERR_INVALID_ARGUMENT;
+  if ((flags & MVS_CONV_T2_LDS) && mode != MVS_CONV_T2) return MVS_ERR_INVALID_ARGUMENT;
   // S2 reads the split cost volume (its 8 bound words in x_bound), S1 / T2 an fp32 region tensor
   const bool s2 = mode == MVS_CONV_S2;
   const int in_flags = MVS_CONV_IN_C4 | MVS_CONV_IN_SPLIT;
@@ -1023,7 +1024,8 @@ int mvs_conv3d_region_split_fwd(int mode, int flags, const float* x, const float
       mode, (flags & MVS_CONV_OUT_NCDHW) != 0, x, x2, weight_frag, weight_exp, y, batch, c_in, c_out, dims, out_origin,
       out_size, io, is, pad, bn_scale, bn_shift, bn_mean, reinterpret_cast<const uint32_t*>(x_bound),
       reinterpret_cast<const uint32_t*>(x2_bound), reinterpret_cast<uint32_t*>(y_bound), (hipStream_t)stream,
-      (flags & MVS_CONV_PER_LANE) != 0, y_addend, store_origin, store_size, stats, y_mid, y_high, in_bn);
+      (flags & MVS_CONV_PER_LANE) != 0, y_addend, store_origin, store_size, stats, y_mid, y_high, in_bn,
+      (flags & MVS_CONV_T2_LDS) != 0);
   if (st != MVS_OK) return st;
   return lc.status();
 }
@@ -1033,8 +1035,10 @@ long long mvs_conv3d_region_split_stats_slots(int mode, int flags, int batch, in
   if (!out_size || batch <= 0 || mode < MVS_CONV_S1 || mode > MVS_CONV_T2) return MVS_ERR_INVALID_ARGUMENT;
   for (int k = 0; k < 3; ++k)
     if (out_size[k] <= 0) return MVS_ERR_INVALID_ARGUMENT;
+  if ((flags & MVS_CONV_T2_LDS) && mode != MVS_CONV_T2) return MVS_ERR_INVALID_ARGUMENT;
   return mvs::conv3d_region_split_slots(mode, batch, c_in, c_out, out_size, (flags & MVS_CONV_PER_LANE) != 0,
-                                        (flags & MVS_CONV_SUM_INPUT) != 0, (flags & MVS_CONV_IN_BN) != 0);
+                                        (flags & MVS_CONV_SUM_INPUT) != 0, (flags & MVS_CONV_IN_BN) != 0,
+                                        (flags & MVS_CONV_T2_LDS) != 0);
 }
 
 

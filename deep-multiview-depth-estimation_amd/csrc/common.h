@@ -13,6 +13,7 @@
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #include "../../include/mvs_cost_volume.h"
 
@@ -293,5 +294,14 @@ class LaunchCheck {
 };
 
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// A numeric tuning override from the environment (atoi of the value; `fallback` when unset), read on every
+// call and clamped by the caller.  The only reads of the environment under csrc/: MVS_CV_CSPLIT
+// (cost_volume_fwd.hip) and MVS_CONV2D_SPLIT (conv2d_narrow.hip), whose entry points have no flags argument.
+// Which kernel variant runs is never decided here: that is the flags' (mvs_amd/eval_switches.py sets them).
+inline int env_int(const char* name, int fallback) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : fallback;
+}
 
 }  // namespace mvs

@@ -15,8 +15,6 @@
 // halo of the tile ((8-1)*S + K rows x (32-1)*S + K columns, zero outside the image) is staged in
 // LDS NC channels per pass; the next pass's elements are loaded into registers before this pass's
 // arithmetic.
-#include <cstdlib>
-
 #include "launchers.h"
 #include "split.h"
 
@@ -158,10 +156,8 @@ void launch2d(const float* in, const float* wt, float* out, int N, int H, int W,
   const long wgs = (long)tiles_x * tiles_y * N;
   int split = 1;
   while (split < MAXS && wgs * split < kSplitTarget) split *= 2;
-  if (const char* e = getenv("MVS_CONV2D_SPLIT")) {
-    const int f = atoi(e);
-    if (f >= 1) split = f > MAXS ? MAXS : f;
-  }
+  const int f = env_int("MVS_CONV2D_SPLIT", 0);
+  if (f >= 1) split = f > MAXS ? MAXS : f;
   const dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)N, (unsigned)split);
   if (split >= 4 && MAXS >= 4)
     hipLaunchKernelGGL((conv2d_narrow_kernel<CIN, COUT, K, S, (MAXS >= 4 ? 4 : 1)>), grid, dim3(kBlock), 0, s, in,

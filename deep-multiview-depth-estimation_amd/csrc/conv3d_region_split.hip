@@ -23,8 +23,6 @@
 // S2 (conv_k_0, model.py:78-80 / :103-111): the input is the split cost volume itself (split.h's SCV,
 // or a box of it), already the operands: a lane's 8 channels are the hi / lo halves of quads 2g and
 // 2g + 1 (two 16-byte loads, no conversion), scaled by the volume's bound words (cv_split_exponent).
-#include <cstdlib>
-
 #include "launchers.h"
 #include "region_conv.h"
 
@@ -868,22 +866,19 @@ static int split_rb(int mode, int B, const int* on, int CO) {
 }
 
 // The LDS-staged transposed kernel for large output regions (train mode's full volumes: T2 64 -> 32
-// 2.41 -> 1.45 ms, 32 -> 16 1.10 -> 0.73 ms); MVS_T2_LDS=0 / 2 forces the per-lane / LDS kernel (A/B
-// and tests)
+// 2.41 -> 1.45 ms, 32 -> 16 1.10 -> 0.73 ms); per_lane (MVS_CONV_PER_LANE) / t2_lds (MVS_CONV_T2_LDS) force
+// the per-lane / LDS kernel (A/B and tests; per_lane wins)
 constexpr long kT2LdsMinVoxels = 1l << 22;
-static bool split_t2_lds(int mode, int B, int CI, int CO, const int* on, bool per_lane, bool has_x2,
-                         bool in_bn = false) {
+static bool split_t2_lds(int mode, int B, int CI, int CO, const int* on, bool per_lane, bool t2_lds, bool in_bn) {
   if (mode != kT2 || !((CI == 64 && CO == 32) || (CI == 32 && CO == 16))) return false;
   if (in_bn) return true;   // the folded input BN + ReLU: this kernel only
-  const char* fe = getenv("MVS_T2_LDS");   // read per call: tests switch it
-  const int force = fe ? atoi(fe) : 1;
-  if (per_lane || force == 0) return false;
-  return force == 2 || (long)B * on[0] * on[1] * on[2] >= kT2LdsMinVoxels;
+  if (per_lane) return false;
+  return t2_lds || (long)B * on[0] * on[1] * on[2] >= kT2LdsMinVoxels;
 }
 
 long conv3d_region_split_slots(int mode, int B, int CI, int CO, const int* on, bool per_lane, bool has_x2,
-                               bool in_bn) {
-  if (split_t2_lds(mode, B, CI, CO, on, per_lane, has_x2, in_bn)) {
+                               bool in_bn, bool t2_lds) {
+  if (split_t2_lds(mode, B, CI, CO, on, per_lane, t2_lds, in_bn)) {
     int tx, ty, tz;
     if (CI == 64) t2_lds_tiles<64, 1>(on, tx, ty, tz);
     else t2_lds_tiles<32, 2>(on, tx, ty, tz);
@@ -906,7 +901,7 @@ int launch_conv3d_region_split(int mode, bool out_cf, const float* x, const floa
                                const float* bn_shift, const float* bn_mean, const uint32_t* x_bound,
                                const uint32_t* x2_bound, uint32_t* y_bound, hipStream_t s, bool per_lane,
                                const float* y_addend, const int* store_origin, const int* store_size,
-                               double* stats, float* y_mid, float* y_high, const float* in_bn) {
+                               double* stats, float* y_mid, float* y_high, const float* in_bn, bool t2_lds) {
   GeoS g;
   g.in_bn = in_bn;
   g.ym[0] = y_mid;
@@ -939,10 +934,10 @@ int launch_conv3d_region_split(int mode, bool out_cf, const float* x, const floa
   }
   // S1: conv_k_1 (16 / 32 / 64 channels; LDS-staged operands per kS1Lds); T2: deconv_3_0 (64 -> 32),
   // deconv_2_0 (32 -> 16); S2: conv_k_0 from the split cost volume (32 -> 16 / 32 / 64)
-  if (in_bn && !split_t2_lds(mode, B, CI, CO, on, per_lane, x2 != nullptr, true) &&
+  if (in_bn && !split_t2_lds(mode, B, CI, CO, on, per_lane, t2_lds, true) &&
       !(split_uses_lds(mode, CI, CO, per_lane, x2 != nullptr) && CI <= 64))
     return MVS_ERR_INVALID_ARGUMENT;   // the folded input BN: the LDS-staged kernels only
-  if (split_t2_lds(mode, B, CI, CO, on, per_lane, x2 != nullptr, in_bn != nullptr)) {
+  if (split_t2_lds(mode, B, CI, CO, on, per_lane, t2_lds, in_bn != nullptr)) {
     if (CI == 64)
       launch_t2_lds<64, 32, 1>(x, x2, wfrag, w_exp, y, bn_scale, bn_shift, bn_mean, B, g, x_bound, x2_bound, y_bound, s);
     else

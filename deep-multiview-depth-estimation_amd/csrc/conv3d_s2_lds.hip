@@ -23,8 +23,6 @@
 //     output i's tap voxel) and one of B (lane (kq, co): the same channels of output channel co's weights)
 //     feed 4 MFMAs (K-step s takes element s of both); the two channel blocks accumulate in two chains
 //     (the 16x16x4 f32 MFMA's 40-cycle dependent latency under its 32-cycle issue), summed at the end.
-#include <cstdlib>
-
 #include "launchers.h"
 #include "packed.h"
 
@@ -209,17 +207,9 @@ __global__ __launch_bounds__(kLThreads) void conv_s2_lds_kernel(
 
 }  // namespace
 
-// Opt-in (MVS_S2_LDS=1): measured slower -- conv_1_0 alone 1.42 against 1.15 ms for the per-lane region
-// kernel, the fp32 eval step 6.8-6.9 against 5.9 ms: its 161 KB of LDS takes a whole CU, so the concurrent
-// VALU conv_0_0 can no longer share the CUs it runs on (gpurun_out r6z)
-bool conv_s2_lds_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("MVS_S2_LDS");
-    return e && e[0] == '1';
-  }();
-  return on;
-}
-
+// Opt-in (the flag MVS_CONV_S2_LDS; mvs_amd.ops sets it with MVS_S2_LDS=1): measured slower -- conv_1_0 alone
+// 1.42 against 1.15 ms for the per-lane region kernel, the fp32 eval step 6.8-6.9 against 5.9 ms: its 161 KB of
+// LDS takes a whole CU, so the concurrent VALU conv_0_0 can no longer share the CUs it runs on
 void launch_conv_s2_lds(const float* x, int in_c4, const float* w27, float* y, int B, const int* n, const int* o0,
                         const int* on, const int* pad, const float* bn_scale, const float* bn_shift,
                         const float* bn_mean, hipStream_t s) {

@@ -21,8 +21,6 @@
 //   * a plane group whose union footprint does not fit the 40 KB LDS budget is processed plane by
 //     plane; a plane that still does not fit samples straight from the packed global features.
 // Workgroup ids are remapped so each XCD walks consecutive (tile, plane group) items.
-#include <cstdlib>
-
 #include "launchers.h"
 #include "split.h"
 #include "packed.h"
@@ -725,11 +723,8 @@ void launch_gather(const Geometry& g, const float* feat, const Cams& cm, float* 
   // small shards: the channel chunks split over 2 workgroups per (tile, plane group) (MVS_CV_CSPLIT, 1..8),
   // then the plane group halved until the grid has the workgroups -- cfg 4's 32-plane shard: 4-plane
   // groups, 2 chunk halves, 43 us against 47 us for 2-plane groups (4: 51, 8: 57 us; gpurun_out r6s)
-  static const int csplit_env = [] {
-    const char* e = getenv("MVS_CV_CSPLIT");
-    const int v = e ? atoi(e) : 2;
-    return v < 1 ? 1 : (v > 8 ? 8 : v);
-  }();
+  const int cs = env_int("MVS_CV_CSPLIT", 2);
+  const int csplit_env = cs < 1 ? 1 : (cs > 8 ? 8 : cs);
   const int csplit = (long)g.B * tiles_x * tiles_y * ((g.Dc + pg - 1) / pg) < kMinWorkgroups ? csplit_env : 1;
   while (pg > 1 && (long)g.B * tiles_x * tiles_y * ((g.Dc + pg - 1) / pg) * csplit < kMinWorkgroups) pg >>= 1;
   const int groups = (g.Dc + pg - 1) / pg;

@@ -86,7 +86,6 @@ void launch_soft_argmin(const float* prob, const float* d_batch, int B, int D, u
 // input is channel-quad in[B][Cin/4][D][H][W][4], fp32 (1) or bf16 (2)
 // wino_z (Cout = 8): Winograd F(2,3) along depth, weight = the transformed wu[Cin][3][3][4][8]
 // csrc/conv3d_s2_lds.hip: conv_1_0 (S2 32 -> 16) from the whole fp32 volume (channel quads or NCDHW), LDS-staged
-bool conv_s2_lds_enabled();
 void launch_conv_s2_lds(const float* x, int in_c4, const float* w27, float* y, int B, const int* n, const int* o0,
                         const int* on, const int* pad, const float* bn_scale, const float* bn_shift,
                         const float* bn_mean, hipStream_t s);
@@ -220,10 +219,10 @@ int launch_conv3d_region_split(int mode, bool out_cf, const float* x, const floa
                                const uint32_t* x2_bound, uint32_t* y_bound, hipStream_t s, bool per_lane = false,
                                const float* y_addend = nullptr, const int* store_origin = nullptr,
                                const int* store_size = nullptr, double* stats = nullptr, float* y_mid = nullptr,
-                               float* y_high = nullptr, const float* in_bn = nullptr);
+                               float* y_high = nullptr, const float* in_bn = nullptr, bool t2_lds = false);
 // workgroups (= float64 sum slots) of the launch launch_conv3d_region_split makes for these arguments
 long conv3d_region_split_slots(int mode, int B, int CI, int CO, const int* on, bool per_lane, bool has_x2,
-                               bool in_bn = false);
+                               bool in_bn = false, bool t2_lds = false);
 
 // channel_ops.hip: train-mode BatchNorm pieces -- per-channel float64 sums into
 // stats[slot][2][C] (64 slots) and y = relu(BN(x)) [+ relu(BN'(r))], channels-last or NCDHW

@@ -28,6 +28,7 @@ MVS_CONV_S1, MVS_CONV_S2, MVS_CONV_T2 = 0, 1, 2
 MVS_CONV_OUT_NCDHW = 1
 MVS_CONV_PER_LANE = 32
 MVS_CONV_S2_LDS = 256
+MVS_CONV_T2_LDS = 512
 MVS_CONV_SUM_INPUT = 64
 MVS_CONV_IN_BN = 128
 MVS_CONV_IN_C4 = 2

@@ -5,11 +5,12 @@ The same names exist here with the same default values, so ``from mvs_amd.config
 is a drop-in; ``MVSConfig`` carries them explicitly for callers that need several geometries
 in one process (the reference cannot: it must be re-imported per geometry).
 """
-import os
 from dataclasses import dataclass, field
 
 import numpy as np
 import torch
+
+from . import eval_switches
 
 ACC_THRESH = 0.05            # config.py:4
 D_SCALE = 25                 # config.py:6  -- plane spacing multiplier of d_int
@@ -63,7 +64,7 @@ class MVSConfig:
 
     def __post_init__(self):
         if self.arithmetic is None:
-            self.arithmetic = os.environ.get("MVS_ARITHMETIC", "fp32")
+            self.arithmetic = eval_switches.arithmetic()
         if self.arithmetic not in ARITHMETICS:
             raise ValueError("arithmetic must be one of %s, got %r" % (ARITHMETICS, self.arithmetic))
         if self.feat_h is None:

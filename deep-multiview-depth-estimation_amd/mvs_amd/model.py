@@ -24,14 +24,13 @@ the reference (``model.py:164-166``) the instance attribute
 The encoder, the refinement net and ``MVSNet`` live here; the regulariser is ``regulariser.py`` (with
 ``regions.py``, ``bn_sums.py`` and ``streams.py``), whose helpers stay importable from this module.
 """
-import os
 import warnings
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import streams, train_switches
+from . import eval_switches, streams, train_switches
 from .bn_sums import _bn_constant, _bn_train, _bn_train_hip, _border_class_sums, _border_tables_u  # noqa: F401
 from .config import MVSConfig
 from .costvolume import warp_and_assemble_cost_volume
@@ -106,8 +105,7 @@ def _run_stack(seq, x, split_f16=False):
     layers = list(seq)
     # split-fp16 MFMA convolutions (csrc/conv2d_split.hip) for the 8..32-channel inputs: every layer's
     # output carries bound words (one zeroed set per layer, one memset) that scale the next layer's input
-    words = (bound_words(len(layers), x.device)
-             if split_f16 and os.environ.get("MVS_CONV2D_F16", "1") != "0" else None)
+    words = bound_words(len(layers), x.device) if split_f16 and eval_switches.conv2d_f16() else None
 
     def conv(layer, x, xb, yb, bn=None):
         """(y, whether yb now bounds y): the HIP convolutions for the reference's layer shapes"""
@@ -238,7 +236,7 @@ class MVSNet(nn.Module):
         self.set_arithmetic(self.cfg.arithmetic)
         # eval inference over B >= 2 samples: chunks of samples issued on their own streams (forward)
         # (measured slower at cfg 2: 6.32 against 5.87 ms per step with 2 chunks, gpurun_out r6f -- off)
-        self.pipeline_chunks = int(os.environ.get("MVS_PIPELINE_CHUNKS", "1"))
+        self.pipeline_chunks = eval_switches.pipeline_chunks()
 
     def set_arithmetic(self, arithmetic):
         """"fp32" (the reference's numerics: every HIP layer in exact fp32) or "split_f16" (opt-in: the
@@ -323,7 +321,7 @@ class MVSNet(nn.Module):
         # materialises the split volume and runs both convolutions in one pass (ops.split_head)
         deferred = split and reg.live_ok(live_n) and (c.d_num % 2 == 0 and n_views in (2, 3)
                                                       and all(p % 2 == 1 for p in reg.pad)
-                                                      and os.environ.get("MVS_CV_HEAD", "0") == "1")
+                                                      and eval_switches.cv_head())
         cost_volume, d_batch, ref_views = warp_and_assemble_cost_volume(
             K_batch, R_batch, T_batch, d_min, d_int, feature_maps, batch_size, n_views,
             d_num=c.d_num, d_scale=c.d_scale,
@@ -348,7 +346,7 @@ class MVSNet(nn.Module):
                 and tuple(ref_img.shape) == (initial_depth_map.shape[0], 3) + tuple(initial_depth_map.shape[2:])
                 and all(t.numel() == 1 or tuple(t.shape) == (initial_depth_map.shape[0], 1, 1, 1)
                         for t in (d_min, d_int))   # per sample [B, 1, 1, 1] (data.py) or one value
-                and os.environ.get("MVS_REFINE_GLUE", "1") != "0"):
+                and eval_switches.refine_glue()):
             # the elementwise steps on either side of the refinement net as one HIP launch each
             # (ops.refine_input / refine_output: 9 launches -> 2, bit-equal to the sequence below)
             from .ops import refine_input, refine_output

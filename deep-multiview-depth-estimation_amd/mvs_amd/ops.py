@@ -20,7 +20,7 @@ from typing import Optional
 
 import torch
 
-from . import _lib
+from . import _lib, eval_switches
 
 _F32 = torch.float32
 
@@ -1368,7 +1368,8 @@ def conv3d_region(x: torch.Tensor, x2: Optional[torch.Tensor], weight: torch.Ten
     BN + ReLU fused when bn_* are given.  ``weight`` is region_weight(module).  ``y_bound``: zeroed
     bound words (int32 [MVS_BOUND_WORDS]) raised to max|y|.  ``per_lane``: the per-lane-operand kernel
     even where an LDS-staged one applies (bit-identical; tests, A/B).  ``s2_lds``: conv_1_0's shape on the
-    LDS-staged stride-2 kernel (MVS_CONV_S2_LDS; opt-in).  Inference only."""
+    LDS-staged stride-2 kernel (MVS_CONV_S2_LDS; opt-in); MVS_S2_LDS=1, read here on every call,
+    asks for it too, where per_lane does not.  Inference only."""
     _require_gpu(x, "x")
     lib = _lib.load()
     quad_bf16 = in_c4 and x.dtype == torch.bfloat16
@@ -1386,7 +1387,8 @@ def conv3d_region(x: torch.Tensor, x2: Optional[torch.Tensor], weight: torch.Ten
     y = torch.empty(shape, device=x.device, dtype=_F32)
     flags = ((_lib.MVS_CONV_OUT_NCDHW if out_ncdhw else 0) | (_lib.MVS_CONV_IN_C4 if in_c4 else 0)
              | (_lib.MVS_CONV_IN_BF16 if quad_bf16 else 0) | (_lib.MVS_CONV_IN_SPLIT if quad_split else 0)
-             | (_lib.MVS_CONV_PER_LANE if per_lane else 0) | (_lib.MVS_CONV_S2_LDS if s2_lds else 0))
+             | (_lib.MVS_CONV_PER_LANE if per_lane else 0)
+             | (_lib.MVS_CONV_S2_LDS if s2_lds or (not per_lane and eval_switches.s2_lds()) else 0))
     st = lib.mvs_conv3d_region_fwd(int(mode), flags, _lib.ptr(x), _opt_ptr(x2), _lib.ptr(w),
                                    _lib.ptr(y), b, cin, cout, _ints3(dims), _ints3(out_origin), _ints3(out_size),
                                    _opt_ints3(in_origin), _opt_ints3(in_size), _opt_ints3(pad), *bp,
@@ -1411,6 +1413,15 @@ BOUND_WORDS = 2048   # MVS_BOUND_WORDS (64 slots, one per 128-byte line)
 def bound_words(n, device):
     """n zeroed bound-word sets (int32 [n, MVS_BOUND_WORDS]) -- one memset for a forward's tensors."""
     return torch.zeros((n, BOUND_WORDS), device=device, dtype=torch.int32)
+
+
+def _kernel_flags(mode, per_lane):
+    """MVS_CONV_PER_LANE from the caller, and for a transposed split convolution from MVS_T2_LDS (read on every
+    call): 0 the per-lane kernel, 2 the LDS-staged one (MVS_CONV_T2_LDS) at every size; per_lane wins."""
+    t2 = eval_switches.t2_lds() if mode == CONV_T2 else 1
+    if per_lane or t2 == 0:
+        return _lib.MVS_CONV_PER_LANE
+    return _lib.MVS_CONV_T2_LDS if t2 == 2 else 0
 
 
 def _bound_ptr(t):
@@ -1456,7 +1467,7 @@ def conv3d_region_split(x: torch.Tensor, x2: Optional[torch.Tensor], weight: tor
     (DESIGN.md §3.8).  Inference only."""
     _require_gpu(x, "x")
     lib = _lib.load()
-    flags = (_lib.MVS_CONV_OUT_NCDHW if out_ncdhw else 0) | (_lib.MVS_CONV_PER_LANE if per_lane else 0)
+    flags = (_lib.MVS_CONV_OUT_NCDHW if out_ncdhw else 0) | _kernel_flags(mode, per_lane)
     if mode == CONV_S2:
         if x.dtype != torch.int32 or x.dim() != 6 or x_bound is None or x_bound.numel() != 8:
             raise ValueError("CONV_S2: the split cost volume [B, 8, D, H, W, 4] int32 and its 8 bound words")
@@ -1527,8 +1538,9 @@ def conv_s2_split_multi_sums(cv, weights, dims, out_origin, out_size, pad, bound
 
 
 def split_stats_slots(mode, batch, c_in, c_out, out_size, per_lane=False, two_inputs=False, in_bn=False):
-    """Sum slots (workgroups) of a conv3d_region_split launch (mvs_conv3d_region_split_stats_slots)."""
-    flags = ((_lib.MVS_CONV_PER_LANE if per_lane else 0) | (_lib.MVS_CONV_SUM_INPUT if two_inputs else 0)
+    """Sum slots (workgroups) of the conv3d_region_split launch with these arguments under the MVS_T2_LDS of
+    this moment (mvs_conv3d_region_split_stats_slots)."""
+    flags = (_kernel_flags(mode, per_lane) | (_lib.MVS_CONV_SUM_INPUT if two_inputs else 0)
              | (_lib.MVS_CONV_IN_BN if in_bn else 0))
     n = _lib.load().mvs_conv3d_region_split_stats_slots(int(mode), flags, int(batch), int(c_in), int(c_out),
                                                        _ints3(out_size))

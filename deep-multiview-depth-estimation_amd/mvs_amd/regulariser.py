@@ -1,13 +1,11 @@
 """The 3-D cost-volume regulariser (reference ``scripts/model.py:68-126``) and the dispatch that decides
 which of its evaluations runs: the fused head, the eval-mode live regions on the HIP kernels or through
 PyTorch's layers, train-mode BatchNorm from sums, the live regions under autograd, or the full volume."""
-import os
-
 import torch
 import torch.nn as nn
 
 from . import config as cfg_mod
-from . import streams
+from . import eval_switches, streams
 from .bn_sums import _apply_bn, _bn_constant, _bn_train, _bn_train_hip, _border_class_sums, _sums
 from .regions import (_conv_s1_region, _conv_s2_region, _crop_cf, _crop_cl, _crop_pad, _grow, _tconv_region,
                       extent, live_regions, origin)
@@ -129,7 +127,7 @@ class CostVolumeReg(nn.Module):
         split-fp16 convolutions, fp32 HIP inference, C = 32, 2-3 views, D even and every stride-2
         padding odd (the kernel's window ownership), MVS_CV_HEAD=1 (opt-in)."""
         n = tuple(dcv.shape[2:])
-        return (os.environ.get("MVS_CV_HEAD", "0") == "1" and self.split_f16 and self.live_ok(n)
+        return (eval_switches.cv_head() and self.split_f16 and self.live_ok(n)
                 and _hip_inference(dcv.feature_maps) and dcv.shape[1] == 32 and dcv.n_views in (2, 3)
                 and n[0] % 2 == 0 and all(p % 2 == 1 for p in self.pad))
 
@@ -249,7 +247,7 @@ class CostVolumeReg(nn.Module):
         # matrix cores (ops.conv3d_region_split, csrc/conv3d_region_split.hip; MVS_REGION_SPLIT=0: the
         # fp32-MFMA kernels): every region tensor they read carries bound words, raised by the kernel
         # that writes it -- rows 0-2 conv_k_0's outputs, 3-5 conv_k_1's, 6 deconv_3_0's (one memset)
-        bw = bound_words(7, cv.device) if split_cv and os.environ.get("MVS_REGION_SPLIT", "1") != "0" else None
+        bw = bound_words(7, cv.device) if split_cv and eval_switches.region_split() else None
         y1_bounded = False
         if head is None and split_cv and self._split_head_ok(cv, n):
             # conv_0_0 + BN_0 + ReLU and conv_1_0 + BN_1 + ReLU in one pass over the split volume
@@ -369,14 +367,14 @@ class CostVolumeReg(nn.Module):
     def _fp32_head_ok(self, cv, c4, pad):
         """ops.conv_head_fp32 applies: the fp32 channel-quad volume of 32 channels, conv_1_0 32 -> 16,
         every stride-2 padding odd (the kernel's window ownership), MVS_FP32_HEAD=1 (opt-in: slower, above)."""
-        return (os.environ.get("MVS_FP32_HEAD", "0") == "1" and c4 and cv.dtype == torch.float32
+        return (eval_switches.fp32_head() and c4 and cv.dtype == torch.float32
                 and cv.dim() == 6 and cv.shape[1] == 8 and tuple(self.conv_1_0.weight.shape[:2]) == (16, 32)
                 and all(p % 2 == 1 for p in pad))
 
     def _split_head_ok(self, cv, n):
         """ops.split_head applies to this split volume: C = 32 (8 channel quads), D even and every
         stride-2 padding odd (the kernel's window ownership), MVS_SPLIT_HEAD not 0."""
-        return (os.environ.get("MVS_SPLIT_HEAD", "1") != "0" and cv.shape[1] == 8 and n[0] % 2 == 0
+        return (eval_switches.split_head() and cv.shape[1] == 8 and n[0] % 2 == 0
                 and all(p % 2 == 1 for p in self.pad))
 
     def forward_live_train(self, cv, bound=None):
@@ -470,8 +468,7 @@ class CostVolumeReg(nn.Module):
         # (conv3d_region_split): their inputs' bound words are raised by the BN + ReLU passes -- rows 0-2
         # the conv_k_1 inputs, 4-5 conv_2_1 / conv_3_1's outputs, 6 deconv_3_0's (raw: the transposed
         # convs fold the BN + ReLU into their staging)
-        bw = (bound_words(7, cv.device) if self.split_f16 and os.environ.get("MVS_REGION_SPLIT", "1") != "0"
-              else None)
+        bw = bound_words(7, cv.device) if self.split_f16 and eval_switches.region_split() else None
         bwr = lambda k: None if bw is None else bw[k]
         org, size = origin, extent
         dims, pad, bsz = list(n), list(self.pad), cv.shape[0]

@@ -505,9 +505,8 @@ int mvs_conv_head_fp32_fwd(const float* cv4, int batch, int d, int h, int w, con
  * words (DEVICE; NULL otherwise).  y_bound: NULL, or MVS_BOUND_WORDS words (DEVICE, zeroed by the
  * caller) raised to max|y| (see mvs_conv3d_region_split_fwd).  Eval-mode inference only; products
  * summed in the order (tap, c_in) -- MIOpen sums them in other orders (fp32 rounding-level differences).
- * MVS_CONV_S1 with c_in = c_out and no x2 runs an LDS-staged kernel (each input voxel loaded once per
- * 16 x 4 x TZ output tile), bit-identical to the per-lane-operand kernel that flags MVS_CONV_PER_LANE
- * (below) selects.  MVS_CONV_T2 (32, 16) runs the cell kernel (csrc/conv3d_region.hip conv3d_t2_cells_kernel: a GEMM
+ * MVS_CONV_S1 runs the per-lane-operand kernel with or without MVS_CONV_PER_LANE (below): this entry point has
+ * no LDS-staged stride-1 kernel (mvs_conv3d_region_split_fwd has).  MVS_CONV_T2 (32, 16) runs the cell kernel (csrc/conv3d_region.hip conv3d_t2_cells_kernel: a GEMM
  * row is a cell (o + pad) >> 1 per dim, whose 2 x 2 x 2 inputs are loaded once into registers and feed all
  * eight output parity classes; no LDS; one or two inputs, either output layout), bit-identical to the
  * parity-class kernel (one pass over the outputs per class, each class fetching its own taps' inputs), which
@@ -525,8 +524,15 @@ int mvs_conv3d_region_fwd(int mode, int flags, const float* x, const float* x2, 
 #define MVS_CONV_PER_LANE 32
 /* flag of mvs_conv3d_region_fwd: conv_1_0's shape (MVS_CONV_S2, c_in 32, c_out 16, the whole fp32 volume,
  * channel quads or NCDHW, channels-last output, no store box) on the LDS-staged kernel (csrc/conv3d_s2_lds.hip;
- * the default only with the environment variable MVS_S2_LDS=1: slower inside the eval step) */
+ * slower inside the eval step; not with MVS_CONV_PER_LANE; ignored for every other shape).  The
+ * library reads no environment variable to choose a kernel: mvs_amd.ops sets this flag when MVS_S2_LDS=1. */
 #define MVS_CONV_S2_LDS 256
+/* flag of mvs_conv3d_region_split_fwd and mvs_conv3d_region_split_stats_slots, MVS_CONV_T2 only (else
+ * MVS_ERR_INVALID_ARGUMENT): the LDS-staged transposed kernel also below the output size (2^22 voxels) from which
+ * it is the default for (c_in, c_out) = (64, 32) and (32, 16); MVS_CONV_PER_LANE selects the per-lane kernel at
+ * every size and wins over this flag; with in_bn the LDS-staged kernel runs whatever the flags (tests and A/B
+ * timing: mvs_amd.ops sets the two flags for MVS_T2_LDS=2 / 0). */
+#define MVS_CONV_T2_LDS 512
 
 /* Bound words of a region tensor: MVS_BOUND_WORDS uint32 (8 KiB) holding maxima of |v| as fp32 bit
  * patterns (the tensor's bound is their maximum), raised with atomic maxima by the kernel that writes
@@ -586,7 +592,7 @@ int mvs_conv3d_region_split_fwd(int mode, int flags, const float* x, const float
 #define MVS_CONV_SUM_INPUT 64
 #define MVS_CONV_IN_BN 128
 /* Number of float64 sum slots (workgroups) of the mvs_conv3d_region_split_fwd call with this mode,
- * flags (MVS_CONV_PER_LANE, MVS_CONV_SUM_INPUT, MVS_CONV_IN_BN), batch, channels and out_size; < 0 on invalid
+ * flags (MVS_CONV_PER_LANE, MVS_CONV_T2_LDS, MVS_CONV_SUM_INPUT, MVS_CONV_IN_BN), batch, channels and out_size; < 0 on invalid
  * arguments.  Host-only: no device work. */
 long long mvs_conv3d_region_split_stats_slots(int mode, int flags, int batch, int c_in, int c_out,
                                               const int* out_size);

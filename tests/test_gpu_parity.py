@@ -791,9 +791,9 @@ def _bn_relu(y, sc, sh, mu):
                                          (64, (24, 20, 26), False, False), (16, (192, 128, 160), True, True),
                                          (32, (192, 128, 160), False, True), (64, (192, 128, 160), False, True)])
 def test_region_s1_lds_kernel_bit_equal_to_per_lane(c, n, ncdhw, bn):
-    """The LDS-staged stride-1 region convolution (conv3d_s1_lds_kernel: the fp32 path's conv_k_1) gives the
-    per-lane-operand kernel's (MVS_CONV_PER_LANE) outputs bit for bit -- same products, same order per
-    accumulator -- and the same bound words, at the live regions of a cfg-1-like and of the cfg-2 volume
+    """The fp32 path's stride-1 region convolution (conv_k_1) with and without MVS_CONV_PER_LANE: the same outputs
+    bit for bit and the same bound words (written when an LDS-staged fp32 kernel, since removed as slower, ran
+    without the flag; today both calls run the per-lane-operand kernel), at the live regions of a cfg-1-like and of the cfg-2 volume
     (level 1 / 2 / 3 regions: ragged 16 x 4 x TZ tiles in every dim), channels-last and channels-first."""
     from mvs_amd.config import pad_outpad
     from mvs_amd.model import _grow, _tconv_input_region

@@ -107,6 +107,25 @@ def test_invalid_arguments_rejected_before_any_launch():
     assert lib.mvs_conv3d_region_split_stats_slots(0, _lib.MVS_CONV_PER_LANE, 2, 16, 16, size) != s1
     assert lib.mvs_conv3d_region_split_stats_slots(3, 0, 2, 16, 16, size) == -1
     assert lib.mvs_conv3d_region_split_stats_slots(0, 0, 0, 16, 16, size) == -1
+    # MVS_CONV_T2_LDS: the LDS-staged transposed kernel below the size where it is the default -- the slot count
+    # follows the kernel that will run: B x ceil(22 / 32) x ceil(18 / 8) x ceil(26 / 4) tiles (t2_lds_tiles)
+    force = _lib.MVS_CONV_T2_LDS
+    assert lib.mvs_conv3d_region_split_stats_slots(2, force, 2, 64, 32, size) == 2 * 1 * 3 * 7 != t2
+    assert lib.mvs_conv3d_region_split_stats_slots(2, 0, 2, 64, 32, size) == t2          # the per-lane grid
+    assert lib.mvs_conv3d_region_split_stats_slots(2, _lib.MVS_CONV_PER_LANE, 2, 64, 32, size) == t2
+    assert lib.mvs_conv3d_region_split_stats_slots(2, force | _lib.MVS_CONV_PER_LANE, 2, 64, 32, size) == t2
+    assert lib.mvs_conv3d_region_split_stats_slots(0, force, 2, 16, 16, size) == -1     # a transposed conv's flag
+    # ... and mvs_conv3d_region_split_fwd accepts the bit for MVS_CONV_T2 only; an unknown bit is still refused
+    # (an output of 2 x 2048^3 voxels: a call whose flags pass is refused as too large, -3, before any launch)
+    i3 = (ctypes.c_int * 3)
+    huge = (i3(2048, 2048, 2048), i3(0, 0, 0), i3(2048, 2048, 2048), i3(0, 0, 0), i3(8, 8, 8), i3(1025, 1025, 1025))
+
+    def split_fwd(mode, flags, c_in, c_out):
+        return lib.mvs_conv3d_region_split_fwd(mode, flags, fake, None, fake, 0, fake, 2, c_in, c_out, *huge, None, None,
+                                               None, fake, None, None, None, None, None, None, None, None, None, null)
+    assert split_fwd(2, 0, 64, 32) == -3 and split_fwd(2, force, 64, 32) == -3
+    assert split_fwd(2, 1 << 12, 64, 32) == -1 and split_fwd(2, force | (1 << 12), 64, 32) == -1
+    assert split_fwd(0, 0, 16, 16) == -3 and split_fwd(0, force, 16, 16) == -1
 
 
 def test_build_is_gfx950_in_tree():

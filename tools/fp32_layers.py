@@ -3,7 +3,7 @@ fp32 arithmetic) at cfg 2 (B=4, fp32 channel-quad cost volume 32 x 192 x 128 x 1
 (back-to-back launches, HIP events), the LDS-staged stride-1 kernels against the per-lane ones (and their
 bit-equality), then the whole fp32 eval step with conv_0_0 on its side stream (as shipped) and serialised.
 
-Usage: python tools/fp32_layers.py [--reps N] [--only NAME[,NAME]]   (env MVS_S2_RB=4 etc. for A/B builds)
+Usage: python tools/fp32_layers.py [--reps N] [--only NAME[,NAME]]   (MVS_LIB_PATH=... for an A/B build)
 """
 import argparse
 import os
