@@ -6,7 +6,9 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <initializer_list>
 
+#include "../../include/fusion/mvs_depth_filter.h"
 #include "../../include/train/mvs_loss.h"
 #include "../../include/train/mvs_region_train.h"
 #include "launchers.h"
@@ -1244,6 +1246,79 @@ int mvs_masked_mae_bwd(const float* gt, const float* initial, const float* refin
   const mvs::LaunchCheck lc;
   mvs::launch_masked_mae_bwd(gt, initial, refined, c0, c1, batch, (size_t)h * (size_t)w, g_initial, g_refined,
                              (hipStream_t)stream);
+  return lc.status();
+}
+
+// ---- depth-map filtering and fusion (depth_filter.hip; include/fusion/mvs_depth_filter.h) ----
+namespace {
+inline bool aligned4(std::initializer_list<const void*> ps) {
+  for (const void* p : ps)
+    if (!p || ((uintptr_t)p & 3u)) return false;
+  return true;
+}
+// MVS_OK when `count` maps of h x w can be indexed by the one-thread-per-pixel launches
+int filter_maps_geometry(int count, int h, int w) {
+  if (count <= 0 || h <= 0 || w <= 0) return MVS_ERR_INVALID_ARGUMENT;
+  const uint64_t hw = (uint64_t)h * (uint64_t)w;
+  if (hw >= (1ull << 31) || (uint64_t)count * hw >= (1ull << 31)) return MVS_ERR_TOO_LARGE;
+  return MVS_OK;
+}
+int filter_pairs_geometry(int n_views, int n_slots) {
+  if (n_views <= 0 || n_slots <= 0 || n_slots > MVS_FILTER_MAX_SLOTS) return MVS_ERR_INVALID_ARGUMENT;
+  if ((uint64_t)n_views * (uint64_t)n_slots >= (1ull << 31)) return MVS_ERR_TOO_LARGE;
+  return MVS_OK;
+}
+}  // namespace
+
+int mvs_photometric_confidence_fwd(const float* prob, const float* depth, const float* d_batch, int batch, int d_num,
+                                   int h, int w, float* conf, void* stream) {
+  if (!aligned4({prob, depth, d_batch, conf}) || d_num < 2) return MVS_ERR_INVALID_ARGUMENT;
+  const int st = filter_maps_geometry(batch, h, w);
+  if (st != MVS_OK) return st;
+  const mvs::LaunchCheck lc;
+  mvs::launch_photometric_confidence(prob, depth, d_batch, batch, d_num, (uint32_t)h * (uint32_t)w, conf,
+                                     (hipStream_t)stream);
+  return lc.status();
+}
+
+size_t mvs_view_pair_matrices_bytes(int n_views, int n_slots) {
+  if (filter_pairs_geometry(n_views, n_slots) != MVS_OK) return 0;
+  return (size_t)n_views * (size_t)n_slots * MVS_FILTER_PAIR_DOUBLES * sizeof(double);
+}
+
+int mvs_view_pair_matrices(const float* K, const float* R, const float* T, const int* pairs, int n_views,
+                           int n_slots, double* matrices, void* stream) {
+  if (!aligned4({K, R, T, pairs}) || !matrices || ((uintptr_t)matrices & 7u)) return MVS_ERR_INVALID_ARGUMENT;
+  const int st = filter_pairs_geometry(n_views, n_slots);
+  if (st != MVS_OK) return st;
+  const mvs::LaunchCheck lc;
+  mvs::launch_view_pair_matrices(K, R, T, pairs, n_views, n_slots, matrices, (hipStream_t)stream);
+  return lc.status();
+}
+
+int mvs_geometric_consistency_fwd(const float* depth, const int* pairs, const double* matrices, int n_views,
+                                  int n_slots, int h, int w, double px_thresh, double rel_thresh, int* n_consistent,
+                                  float* depth_avg, void* stream) {
+  if (!aligned4({depth, pairs, n_consistent, depth_avg}) || !matrices || ((uintptr_t)matrices & 7u))
+    return MVS_ERR_INVALID_ARGUMENT;
+  if (!(px_thresh > 0.0 && std::isfinite(px_thresh) && rel_thresh > 0.0 && std::isfinite(rel_thresh)))
+    return MVS_ERR_INVALID_ARGUMENT;
+  int st = filter_pairs_geometry(n_views, n_slots);
+  if (st == MVS_OK) st = filter_maps_geometry(n_views, h, w);
+  if (st != MVS_OK) return st;
+  const mvs::LaunchCheck lc;
+  mvs::launch_geometric_consistency(depth, pairs, matrices, n_views, n_slots, h, w, px_thresh, rel_thresh,
+                                    n_consistent, depth_avg, (hipStream_t)stream);
+  return lc.status();
+}
+
+int mvs_backproject_fwd(const float* depth, const float* K, const float* R, const float* T, int n_views, int h,
+                        int w, float* xyz, void* stream) {
+  if (!aligned4({depth, K, R, T, xyz})) return MVS_ERR_INVALID_ARGUMENT;
+  const int st = filter_maps_geometry(n_views, h, w);
+  if (st != MVS_OK) return st;
+  const mvs::LaunchCheck lc;
+  mvs::launch_backproject(depth, K, R, T, n_views, h, w, xyz, (hipStream_t)stream);
   return lc.status();
 }
 

@@ -260,6 +260,18 @@ void launch_masked_mae_fwd(const float* gt, const float* x0, const float* x1, in
 void launch_masked_mae_bwd(const float* gt, const float* x0, const float* x1, const float* c0, const float* c1, int B,
                            size_t n, float* g0, float* g1, hipStream_t st);
 
+// depth_filter.hip: depth-map filtering and fusion (mvs_photometric_confidence_fwd, mvs_view_pair_matrices,
+// mvs_geometric_consistency_fwd, mvs_backproject_fwd).  One thread per output element, every element written once.
+// pairs [N][S] int32 (an entry outside [0, N) or naming its own view is an empty slot); mats [N][S][24] doubles
+void launch_photometric_confidence(const float* prob, const float* depth, const float* d_batch, int B, int D,
+                                   uint32_t hw, float* conf, hipStream_t s);
+void launch_view_pair_matrices(const float* K, const float* R, const float* T, const int* pairs, int N, int S,
+                               double* out, hipStream_t s);
+void launch_geometric_consistency(const float* depth, const int* pairs, const double* mats, int N, int S, int h, int w,
+                                  double px_thresh, double rel_thresh, int* count, float* avg, hipStream_t s);
+void launch_backproject(const float* depth, const float* K, const float* R, const float* T, int N, int h, int w,
+                        float* xyz, hipStream_t s);
+
 // dtu_input.hip: data.py:206-210 image normalisation (uint8 HWC -> fp32 NCHW), data.py:300-301
 // depth thresholds
 void launch_normalize_images(const uint8_t* rgb, int n, uint32_t hw, const float* mean3,

@@ -1,5 +1,6 @@
 """ctypes binding of the C ABI in ``include/mvs_cost_volume.h`` and of its training extension
-``include/train/mvs_region_train.h`` and ``include/train/mvs_loss.h`` (libmvs_cost_volume.so).
+``include/train/mvs_region_train.h`` and ``include/train/mvs_loss.h``, and of the depth-map filtering entry points
+in ``include/fusion/mvs_depth_filter.h`` (libmvs_cost_volume.so).
 
 The library is built in-tree by ``mvs_amd._build.build_library()`` (called from
 ``__graft_entry__.build()``) and travels to the GPU box as a file next to this module.  There is
@@ -141,6 +142,18 @@ LOSS_SIGNATURES = {
 }
 
 
+# depth-map filtering and fusion (include/fusion/mvs_depth_filter.h): additive, under mvs_abi_version
+_c_double = ctypes.c_double
+FILTER_MAX_SLOTS = 64
+FILTER_SIGNATURES = {
+    "mvs_photometric_confidence_fwd": (_c_int, [_p, _p, _p] + [_c_int] * 4 + [_p, _p]),
+    "mvs_view_pair_matrices_bytes": (ctypes.c_size_t, [_c_int, _c_int]),
+    "mvs_view_pair_matrices": (_c_int, [_p] * 4 + [_c_int, _c_int, _p, _p]),
+    "mvs_geometric_consistency_fwd": (_c_int, [_p] * 3 + [_c_int] * 4 + [_c_double, _c_double, _p, _p, _p]),
+    "mvs_backproject_fwd": (_c_int, [_p] * 4 + [_c_int] * 3 + [_p, _p]),
+}
+
+
 class MVSLibraryError(RuntimeError):
     """The HIP library is missing, stale, or a kernel call failed."""
 
@@ -158,7 +171,7 @@ def load():
             "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950); there is no CPU fallback" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for table in (SIGNATURES, TRAIN_SIGNATURES, LOSS_SIGNATURES):
+    for table in (SIGNATURES, TRAIN_SIGNATURES, LOSS_SIGNATURES, FILTER_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)
             fn.restype = res

@@ -297,7 +297,16 @@ class MVSNet(nn.Module):
             ref.record_stream(main)
         return torch.cat([o[1] for o in outs]), torch.cat([o[2] for o in outs])
 
-    def _forward_one(self, nn_input, K_batch, R_batch, T_batch, d_min, d_int, batch_size, n_views):
+    def forward_with_confidence(self, nn_input, K_batch, R_batch, T_batch, d_min, d_int, batch_size, n_views):
+        """forward's arguments; (initial, refined, confidence): forward's two depth maps and the photometric
+        confidence [B, 1, h, w] of the initial one (fusion.photometric_confidence: the probability mass of the four
+        hypothesis planes around it), taken from the probability volume before it is dropped.  Always the
+        one-stream forward (_forward_one), whatever pipeline_chunks says; HIP device tensors only."""
+        return self._forward_one(nn_input, K_batch, R_batch, T_batch, d_min, d_int, batch_size, n_views,
+                                 with_confidence=True)
+
+    def _forward_one(self, nn_input, K_batch, R_batch, T_batch, d_min, d_int, batch_size, n_views,
+                     with_confidence=False):
         c = self.cfg
         device = nn_input.device
         feature_maps = self.feature_encoder(nn_input)
@@ -333,6 +342,12 @@ class MVSNet(nn.Module):
             cost_volume = cost_volume.float()
         prob_volume = self.cost_volume_reg(cost_volume)
         initial_depth_map = extract_depth_map(prob_volume, d_batch, c.n_depth_est)
+        if with_confidence:
+            from .fusion import photometric_confidence
+            confidence = photometric_confidence(prob_volume, initial_depth_map, d_batch)
+            del prob_volume
+            return (initial_depth_map, self.refine(nn_input, initial_depth_map, d_min, d_int, ref_views),
+                    confidence)
         return initial_depth_map, self.refine(nn_input, initial_depth_map, d_min, d_int, ref_views)
 
     def refine(self, nn_input, initial_depth_map, d_min, d_int, ref_views):

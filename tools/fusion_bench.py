@@ -1,0 +1,181 @@
+"""Device times of the depth-map filtering kernels (mvs_amd.fusion) beside the float64 torch expression they
+replace, run on the same device: profiles/fusion_kernels.txt is this tool's output.
+
+  python tools/fusion_bench.py [--rounds 5] [--iters 50] [--out FILE]
+
+Two sizes: a DTU scan (N = 49 views, S = 10 sources, 128 x 160 maps; the confidence at B = 49, D = 48) and the cfg-5
+map size (N = 5, S = 4, 296 x 400; D = 48).  Per size and kernel: a warm-up, then ``rounds`` alternations of (kernel x
+iters, torch expression x max(1, iters / 10)), each timed with one event pair around the loop; the median per-call
+time over the rounds and the min .. max spread are printed.  The torch expression follows the same definitions
+(include/fusion/mvs_depth_filter.h) in float64 tensor ops, the pairs in a Python loop as a user would write it."""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(REPO, "deep-multiview-depth-estimation_amd"))
+sys.path.insert(0, os.path.join(REPO, "tests"))
+
+import fusion_ref  # noqa: E402
+from mvs_amd import fusion  # noqa: E402
+
+DEV = torch.device("cuda:0")
+F64 = torch.float64
+
+
+def torch_pair_matrices(K, R, T, table):
+    """[N, S, 24] float64 as mvs_view_pair_matrices (zeros for an empty slot)."""
+    K, R, T = K.to(F64), R.to(F64), T.to(F64).reshape(-1, 3, 1)
+    N, S = table.shape
+    n = torch.arange(N, device=K.device).reshape(N, 1).expand(N, S)
+    empty = (table < 0) | (table >= N) | (table == n)
+    s = torch.where(empty, n, table.long())
+
+    def one(a, b):
+        M = (K[b] @ R[b]) @ (R[a].transpose(-1, -2) @ torch.linalg.inv(K[a]))
+        m = K[b] @ (T[b] - (R[b] @ R[a].transpose(-1, -2)) @ T[a])
+        return torch.cat([M.reshape(N, S, 9), m.reshape(N, S, 3)], -1)
+    out = torch.cat([one(n, s), one(s, n)], -1)
+    return torch.where(empty.unsqueeze(-1), torch.zeros_like(out), out)
+
+
+def torch_consistency(depth, mats, table, px, rel):
+    """(count, avg) as mvs_geometric_consistency_fwd, float64 tensor ops, a Python loop over views and slots."""
+    N, _, h, w = depth.shape
+    ys, xs = torch.meshgrid(torch.arange(h, device=depth.device, dtype=F64),
+                            torch.arange(w, device=depth.device, dtype=F64), indexing="ij")
+    tab = table.cpu().tolist()
+    counts, avgs = [], []
+    for n in range(N):
+        d = depth[n, 0].to(F64)
+        valid = d > 0
+        total = torch.zeros_like(d)
+        cnt = torch.zeros_like(d, dtype=torch.int32)
+        for s, src in enumerate(tab[n]):
+            if src < 0 or src >= N or src == n:
+                continue
+            M = mats[n, s]
+            pz = d * (M[6] * xs + M[7] * ys + M[8]) + M[11]
+            alive = valid & (pz > 0)
+            x = (d * (M[0] * xs + M[1] * ys + M[2]) + M[9]) / pz
+            y = (d * (M[3] * xs + M[4] * ys + M[5]) + M[10]) / pz
+            x0, y0 = torch.floor(x), torch.floor(y)
+            alive = alive & (x0 >= 0) & (x0 <= w - 2) & (y0 >= 0) & (y0 <= h - 2)
+            ix = torch.where(alive, x0, torch.zeros_like(x0)).long()
+            iy = torch.where(alive, y0, torch.zeros_like(y0)).long()
+            S = depth[src, 0]
+            ix1, iy1 = (ix + 1).clamp(max=w - 1), (iy + 1).clamp(max=h - 1)
+            t00, t01, t10, t11 = S[iy, ix], S[iy, ix1], S[iy1, ix], S[iy1, ix1]
+            alive = alive & (t00 > 0) & (t01 > 0) & (t10 > 0) & (t11 > 0)
+            fx, fy = x - x0, y - y0
+            ds = (1 - fy) * ((1 - fx) * t00.to(F64) + fx * t01.to(F64)) + fy * ((1 - fx) * t10.to(F64) + fx * t11.to(F64))
+            qz = ds * (M[18] * x + M[19] * y + M[20]) + M[23]
+            alive = alive & (qz > 0)
+            xr = (ds * (M[12] * x + M[13] * y + M[14]) + M[21]) / qz
+            yr = (ds * (M[15] * x + M[16] * y + M[17]) + M[22]) / qz
+            ok = alive & ((xr - xs) ** 2 + (yr - ys) ** 2 < px * px) & ((qz - d).abs() < rel * d)
+            total = total + torch.where(ok, qz, torch.zeros_like(qz))
+            cnt = cnt + ok.to(torch.int32)
+        counts.append(torch.where(valid, cnt, torch.zeros_like(cnt)))
+        avgs.append(torch.where(valid, (d + total) / (1 + cnt), torch.zeros_like(d)).to(torch.float32))
+    return torch.stack(counts).unsqueeze(1), torch.stack(avgs).unsqueeze(1)
+
+
+def torch_confidence(prob, depth, db):
+    B, _, D, h, w = prob.shape
+    db = db.to(F64).expand(B, D)
+    t = (depth.to(F64) - db[:, 0].reshape(B, 1, 1, 1)) / (db[:, 1] - db[:, 0]).reshape(B, 1, 1, 1)
+    k0 = torch.floor(torch.nan_to_num(t)).clamp(0, D - 1).long()
+    conf = torch.zeros_like(t)
+    for k in range(-1, 3):
+        kk = k0 + k
+        inside = (kk >= 0) & (kk < D)
+        conf = conf + torch.where(inside, torch.gather(prob[:, 0], 1, kk.clamp(0, D - 1)).to(F64), torch.zeros_like(t))
+    return torch.where(torch.isnan(t), torch.zeros_like(conf), conf).to(torch.float32)
+
+
+def torch_backproject(depth, K, R, T):
+    N, _, h, w = depth.shape
+    ys, xs = torch.meshgrid(torch.arange(h, device=depth.device, dtype=F64),
+                            torch.arange(w, device=depth.device, dtype=F64), indexing="ij")
+    pix = torch.stack([xs, ys, torch.ones_like(xs)], -1).reshape(1, h * w, 3)
+    d = depth.to(F64).reshape(N, h * w, 1)
+    cam = d * (pix @ torch.linalg.inv(K.to(F64)).transpose(-1, -2)) - T.to(F64).reshape(N, 1, 3)
+    xyz = torch.where(d > 0, cam @ R.to(F64), torch.zeros_like(cam))
+    return xyz.reshape(N, h, w, 3).to(torch.float32)
+
+
+def timed(fn, iters):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / iters * 1e3          # microseconds per call
+
+
+def ab(name, kernel, expression, rounds, iters, emit):
+    slow = max(1, iters // 10)
+    timed(kernel, 10)
+    timed(expression, 2)
+    k, e = [], []
+    for _ in range(rounds):
+        k.append(timed(kernel, iters))
+        e.append(timed(expression, slow))
+    emit("  %-24s kernel %9.1f us (%.1f .. %.1f)   torch float64 %11.1f us (%.1f .. %.1f)   x%.0f"
+         % (name, np.median(k), min(k), max(k), np.median(e), min(e), max(e), np.median(e) / np.median(k)))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--out")
+    args = ap.parse_args()
+    lines = []
+
+    def emit(s):
+        print(s, flush=True)
+        lines.append(s)
+    emit("depth-map filtering kernels on %s: median per-call device time over %d rounds (min .. max), %d calls a round"
+         % (torch.cuda.get_device_name(0), args.rounds, args.iters))
+    for label, N, S, h, w, D in (("DTU scan", 49, 10, 128, 160, 48), ("cfg-5 maps", 5, 4, 296, 400, 48)):
+        emit("%s: N = %d, S = %d, %d x %d, D = %d" % (label, N, S, h, w, D))
+        K, R, T = fusion_ref.arc_cameras(N, h, w, spread=0.25 / N, growth=0.1 / N)
+        depth = torch.from_numpy(fusion_ref.plane_depths(K, R, T, h, w)).to(DEV)
+        K, R, T = (torch.from_numpy(a).to(DEV) for a in (K, R, T))
+        T = T.reshape(N, 3)
+        table = torch.tensor([[(n + 1 + k) % N for k in range(S)] for n in range(N)], dtype=torch.int32, device=DEV)
+        mats = fusion.view_pair_matrices(K, R, T, table)
+        # the two agree before either is timed
+        assert torch.allclose(mats, torch_pair_matrices(K, R, T, table), rtol=1e-9, atol=1e-9)
+        c0, a0 = fusion.geometric_consistency_op(depth, table, mats, 1.0, 0.01)
+        c1, a1 = torch_consistency(depth, mats, table, 1.0, 0.01)
+        assert (c0 != c1).float().mean().item() < 1e-3 and float(c0.float().mean()) > 0.5 * S
+        g = torch.Generator().manual_seed(0)
+        prob = torch.softmax(torch.randn(N, 1, D, h, w, generator=g), 2).to(DEV)
+        db = (425.0 + 2.5 * torch.arange(D, dtype=torch.float32)).reshape(1, D).to(DEV)
+        dep = (425.0 + 2.5 * D * torch.rand(N, 1, h, w, generator=g)).to(DEV)
+        assert torch.allclose(fusion.photometric_confidence(prob, dep, db), torch_confidence(prob, dep, db), atol=1e-6)
+        assert torch.allclose(fusion.backproject(depth, K, R, T), torch_backproject(depth, K, R, T), rtol=1e-6, atol=1e-4)
+        emit("  (mean n_consistent %.2f of %d)" % (float(c0.float().mean()), S))
+        ab("photometric confidence", lambda: fusion.photometric_confidence_op(prob, dep, db),
+           lambda: torch_confidence(prob, dep, db), args.rounds, args.iters, emit)
+        ab("pair matrices", lambda: fusion.view_pair_matrices(K, R, T, table),
+           lambda: torch_pair_matrices(K, R, T, table), args.rounds, args.iters, emit)
+        ab("geometric consistency", lambda: fusion.geometric_consistency_op(depth, table, mats, 1.0, 0.01),
+           lambda: torch_consistency(depth, mats, table, 1.0, 0.01), args.rounds, args.iters, emit)
+        ab("back-projection", lambda: fusion.backproject_op(depth, K, R, T),
+           lambda: torch_backproject(depth, K, R, T), args.rounds, args.iters, emit)
+    emit("(kernel times include the op call's host side: the loop is launch-bound where a kernel is shorter than it)")
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
