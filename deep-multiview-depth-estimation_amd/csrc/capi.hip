@@ -8,6 +8,7 @@
 #include <cstring>
 #include <initializer_list>
 
+#include "../../include/eval/mvs_region_launch.h"
 #include "../../include/fusion/mvs_depth_filter.h"
 #include "../../include/train/mvs_loss.h"
 #include "../../include/train/mvs_region_train.h"
@@ -937,6 +938,17 @@ int mvs_conv3d_region_fwd(int mode, int flags, const float* x, const float* x2, 
                                            nullptr, nullptr, (flags & MVS_CONV_S2_LDS) != 0);
   if (st != MVS_OK) return st;
   return lc.status();
+}
+
+int mvs_conv3d_s2_cells_geometry(int c_in, int c_out, const int* out_size, long long* geometry) {
+  if (!out_size || !geometry || c_in <= 0 || c_out <= 0) return MVS_ERR_INVALID_ARGUMENT;
+  uint64_t ovox = 1;
+  for (int k = 0; k < 3; ++k) {
+    if (out_size[k] <= 0) return MVS_ERR_INVALID_ARGUMENT;
+    ovox *= (uint64_t)out_size[k];
+  }
+  if (ovox >= (1ull << 31)) return MVS_ERR_TOO_LARGE;
+  return mvs::conv3d_s2_cells_geometry(c_in, c_out, out_size, geometry);
 }
 
 int mvs_conv3d_region_split_weights(const float* weight, int c_in, int c_out, unsigned short* frag, int* weight_exp) {

@@ -29,6 +29,9 @@
 #include "launchers.h"
 #include "region_conv.h"
 
+#include <type_traits>
+#include <utility>
+
 namespace mvs {
 namespace {
 
@@ -529,6 +532,213 @@ void launch_t2_cells(const float* x, const float* x2, const float* w, float* y, 
     hipLaunchKernelGGL((conv3d_t2_cells_kernel<CI, CO, RB, false>), grid, dim3(kBlock), 0, s, x, x2, w, y, sc, sh, mu, g);
 }
 
+template <int V>
+using Const = std::integral_constant<int, V>;
+template <int... U, class F>
+__device__ __forceinline__ void static_for(std::integer_sequence<int, U...>, F&& f) {
+  (f(Const<U>{}), ...);
+}
+
+// the cell kernel's sub-steps in order: input rows (iz, iy) ascending, channel blocks, then the cell's outputs
+// (dz, dy) whose tap (iz - 2 dz, iy - 2 dy) lies in the 3 x 3 window -- CZ CY 9 CB of them
+template <int CZ, int CY, int CB>
+struct S2CellSteps {
+  static constexpr int kSubs = CZ * CY * 9 * CB;
+  // sub-step u's (step, dz, dy), packed: found by enumeration
+  static constexpr int find(int u) {
+    int k = 0;
+    for (int st = 0; st < (2 * CZ + 1) * (2 * CY + 1) * CB; ++st) {
+      const int iz = st / ((2 * CY + 1) * CB), iy = st / CB % (2 * CY + 1);
+      for (int dz = 0; dz < CZ; ++dz)
+        for (int dy = 0; dy < CY; ++dy) {
+          const int tz = iz - 2 * dz, ty = iy - 2 * dy;
+          if (tz < 0 || tz > 2 || ty < 0 || ty > 2) continue;
+          if (k++ == u) return (st * CZ + dz) * CY + dy;
+        }
+    }
+    return -1;
+  }
+  static constexpr int step(int u) { return find(u) / (CZ * CY); }
+  static constexpr int dz(int u) { return find(u) / CY % CZ; }
+  static constexpr int dy(int u) { return find(u) % CY; }
+};
+
+// ---- stride-2 convolutions, register-tiled z x y output cells (conv_1_0) ----
+// In the per-lane kernel above every output fetches its own 3 x 3 input rows (tz, ty): the row the outputs
+// y' and y' + 1 share, and the plane z' and z' + 1 share, are loaded again by another wave, often another
+// workgroup -- 9 input rows per output, and whether the repeats hit L2 is timing.  Here a GEMM row is a CELL of
+// CZ x CY outputs in (z, y) at one output x: its outputs read the (2 CZ + 1) x (2 CY + 1) input rows
+// 2 o - P + t of the cell's first output o, so the lane loads each of them once (the three x taps together,
+// per 16-channel block, the per-lane kernel's loads) and feeds every accumulator that reads the row with the
+// weights of its own tap (tz, ty) = (iz - 2 dz, iy - 2 dy) -- 25 / 4 rows per output for 2 x 2 cells.  No LDS,
+// no barriers.  Rows are the flattened (cell-z, cell-y, x) index of the output region, 16 consecutive rows an
+// MFMA row block, RB row blocks per wave (they share the weight loads); only an odd extent in z or y leaves
+// half-empty cells (computed, not stored).  Each lane has its own base voxel and per-dim masks of the input
+// rows / x taps that exist in the (boxed) volume, as region_conv: a missing input reads 0 through kOob.
+// Order: input rows ascending (iz, iy); per accumulator that is ascending (tz, ty), then channel block, then
+// tx, then K-step -- region_conv<kS2>'s products in region_conv<kS2>'s order, with the same zero operands:
+// every output is bit-equal to the per-lane kernel's.
+template <int CI, int CO, int CZ, int CY, int RB, int QM>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) void conv3d_s2_cells_kernel(
+    const float* __restrict__ x, const float* __restrict__ w, float* __restrict__ y,
+    const float* __restrict__ bn_scale, const float* __restrict__ bn_shift, const float* __restrict__ bn_mean,
+    Geo g) {
+  constexpr int NB = CO / 16, CB = CI / 16, NZ = 2 * CZ + 1, NY = 2 * CY + 1;
+  static_assert(CI % 16 == 0 && CO % 16 == 0, "channel counts in multiples of 16");
+  static_assert(QM == 0 || QM == 1, "the fp32 volume: NCDHW or channel quads");
+  const int lane = (int)threadIdx.x & 63;
+  const int m = lane & 15, kq = lane >> 4;
+  const int b = (int)blockIdx.z;
+
+  const int ncy = (g.on[1] + CY - 1) / CY;
+  const int rows = ((g.on[0] + CZ - 1) / CZ) * ncy * g.on[2];
+  const int bx = xcd_work_id((int)blockIdx.x, (int)gridDim.x);
+  const int row0 = (bx * (kBlock / 64) + ((int)threadIdx.x >> 6)) * (16 * RB);
+  if (row0 >= rows) return;   // wave-uniform; no barriers in this kernel
+
+  // per row block: the input voxel of the cell's first output's tap (0, 0, 0) in the addressed box (linear,
+  // may be negative: masked) and, per dim, which of the cell's input rows / x taps exist
+  int lin[RB];
+  unsigned vm[RB][3];
+#pragma unroll
+  for (int rb = 0; rb < RB; ++rb) {
+    const int r = row0 + rb * 16 + m;
+    const bool ok = r < rows;
+    const int rr = ok ? r : 0;
+    const int jx = rr % g.on[2], c = rr / g.on[2];
+    const int o[3] = {g.o0[0] + (c / ncy) * CZ, g.o0[1] + (c % ncy) * CY, g.o0[2] + jx};
+    constexpr int cnt[3] = {NZ, NY, 3};
+    int bs[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      bs[d] = 2 * o[d] - g.pad[d] - g.i0[d];   // taps off the box: off the volume
+      unsigned mk = 0;
+#pragma unroll
+      for (int i = 0; i < cnt[d]; ++i) mk |= (ok && bs[d] + i >= 0 && bs[d] + i < g.in[d]) ? (1u << i) : 0u;
+      vm[rb][d] = mk;
+    }
+    lin[rb] = (bs[0] * g.in[1] + bs[1]) * g.in[2] + bs[2];
+  }
+
+  f4v acc[CZ * CY][RB][NB];
+#pragma unroll
+  for (int c = 0; c < CZ * CY; ++c)
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) acc[c][rb][nb] = f4v{0.0f, 0.0f, 0.0f, 0.0f};
+
+  const size_t rvol = (size_t)g.in[0] * g.in[1] * g.in[2];   // voxels of the (boxed) volume per plane
+  const int sy = g.in[2], sz = g.in[1] * g.in[2];
+  // ---- K loop, software-pipelined by hand (left to itself the scheduler hoists every load of the unrolled
+  // loop and spills): a STEP is an input row (iz, iy) and channel block -- its three x taps, loaded once; a
+  // SUB-STEP is one accumulator (dz, dy) reading it, with its own tap row's weights.  The next step's inputs
+  // and the next sub-step's weights are issued ahead of the current sub-step's MFMAs, and nothing moves
+  // across a sub-step's end ----
+  using T = S2CellSteps<CZ, CY, CB>;
+  f4v a[2][3][RB], bw[2][3][NB];
+  auto load_a = [&](auto step) {   // step st = (iz * NY + iy) * CB + cb
+    constexpr int st = decltype(step)::value, iz = st / (NY * CB), iy = st / CB % NY, cb = st % CB;
+    // the sample's 4 channel quads / 16 channel planes of this block: out-of-range offsets read 0
+    const Rsrc rs = QM == 1 ? make_rsrc(x + ((size_t)b * (CI / 4) + cb * 4) * rvol * 4, (uint32_t)(rvol * 64))
+                            : make_rsrc(x + ((size_t)b * CI + cb * 16) * rvol, (uint32_t)(rvol * 64));
+#pragma unroll
+    for (int tx = 0; tx < 3; ++tx)
+#pragma unroll
+      for (int rb = 0; rb < RB; ++rb) {
+        const bool ok = ((vm[rb][0] >> iz) & (vm[rb][1] >> iy) & (vm[rb][2] >> tx) & 1u) != 0;
+        const uint32_t vx = (uint32_t)(lin[rb] + iz * sz + iy * sy + tx);
+        if constexpr (QM == 1) {   // the quad (c4 / 4) of the voxel: one 16-byte load
+          a[st & 1][tx][rb] = ld4(rs, ok ? ((uint32_t)kq * (uint32_t)rvol + vx) * 16u : kOob, 0);
+        } else {
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            a[st & 1][tx][rb][q] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
+                rs, (int)(ok ? ((uint32_t)(kq * 4 + q) * (uint32_t)rvol + vx) * 4u : kOob), 0, 0));
+        }
+      }
+  };
+  auto load_w = [&](auto sub) {   // sub-step u: tap row (tz, ty) = (iz - 2 dz, iy - 2 dy), w[tap][co][ci]
+    constexpr int u = decltype(sub)::value, st = T::step(u);
+    constexpr int tz = st / (NY * CB) - 2 * T::dz(u), ty = st / CB % NY - 2 * T::dy(u);
+    // (a tap row's weights are read by CZ CY sub-steps far apart: the lane's offset goes through an empty asm
+    // so that the compiler loads them again instead of keeping all 27 taps' weights in registers)
+    int wo = m * CI + kq * 4;
+    asm volatile("" : "+v"(wo));
+#pragma unroll
+    for (int tx = 0; tx < 3; ++tx) {
+      const float* wt = w + (size_t)((tz * 3 + ty) * 3 + tx) * CO * CI + (st % CB) * 16;
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) bw[u & 1][tx][nb] = *reinterpret_cast<const f4v*>(wt + nb * 16 * CI + wo);
+    }
+  };
+  load_a(Const<0>{});
+  load_w(Const<0>{});
+  static_for(std::make_integer_sequence<int, T::kSubs>{}, [&](auto sub) {   // (compile-time u: registers only)
+    constexpr int u = decltype(sub)::value, st = T::step(u), c = T::dz(u) * CY + T::dy(u);
+    if constexpr (u + 1 < T::kSubs) load_w(Const<u + 1>{});
+    if constexpr ((u == 0 || T::step(u > 0 ? u - 1 : 0) != st) && st + 1 < NZ * NY * CB) load_a(Const<st + 1>{});
+#pragma unroll
+    for (int tx = 0; tx < 3; ++tx)
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+          for (int nb = 0; nb < NB; ++nb)
+            acc[c][rb][nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[st & 1][tx][rb][s], bw[u & 1][tx][nb][s],
+                                                                  acc[c][rb][nb], 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+  });
+
+  // ---- epilogue: eval BN + ReLU; acc[cell output][rb][nb][r] = (row kq * 4 + r of the row block, channel
+  // nb * 16 + m), masked to the region (the clipped last cells in z and y) ----
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb) {
+    const int co = nb * 16 + m;
+    const float sc = bn_scale ? bn_scale[co] : 1.0f, sh = bn_scale ? bn_shift[co] : 0.0f,
+                mu = bn_scale ? bn_mean[co] : 0.0f;
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = row0 + rb * 16 + kq * 4 + r;
+        if (row >= rows) continue;
+        const int jx = row % g.on[2], c = row / g.on[2];
+#pragma unroll
+        for (int dz = 0; dz < CZ; ++dz)
+#pragma unroll
+          for (int dy = 0; dy < CY; ++dy) {
+            const int vz = (c / ncy) * CZ + dz, vy = (c % ncy) * CY + dy;
+            if (vz >= g.on[0] || vy >= g.on[1]) continue;
+            float v = acc[dz * CY + dy][rb][nb][r];
+            if (bn_scale) v = fmaxf((v - mu) * sc + sh, 0.0f);
+            store_out(y, g, b, co, vz, vy, jx, CO, v);
+          }
+      }
+  }
+}
+
+// 2 x 2 cells, two row blocks per wave: 155 VGPRs from channel quads, 162 from NCDHW, no scratch, three waves per
+// SIMD (the attribute above holds the compiler to them).  The row blocks share each sub-step's weight loads, and
+// that is what decides: at cfg 2 conv_1_0 alone takes 1.15 ms on the per-lane kernel, 1.00 ms here, and 1.28 /
+// 1.31 / 1.30 ms with one row block per wave and cells of 2 x 2 / 2 x 4 / 4 x 4 (97 / 117 / 151 VGPRs) -- fewer
+// input loads but one set of weight loads per 12 MFMAs instead of per 24; 2 x 4 cells with two row blocks spill
+// 
+constexpr int kS2CellZ = 2, kS2CellY = 2, kS2CellRB = 2;
+
+template <int CI, int CO>
+void launch_s2_cells(const float* x, int in_c4, const float* w, float* y, const float* sc, const float* sh,
+                     const float* mu, int B, const Geo& g, hipStream_t s) {
+  const dim3 grid = s2_cell_grid(kS2CellZ, kS2CellY, kS2CellRB, B, g.on);
+  if (in_c4)
+    hipLaunchKernelGGL((conv3d_s2_cells_kernel<CI, CO, kS2CellZ, kS2CellY, kS2CellRB, 1>), grid, dim3(kBlock), 0, s,
+                       x, w, y, sc, sh, mu, g);
+  else
+    hipLaunchKernelGGL((conv3d_s2_cells_kernel<CI, CO, kS2CellZ, kS2CellY, kS2CellRB, 0>), grid, dim3(kBlock), 0, s,
+                       x, w, y, sc, sh, mu, g);
+}
+
 }  // namespace
 
 int launch_conv3d_region(int mode, bool out_cf, int in_c4, const float* x, const float* x2, const float* w,
@@ -563,6 +773,11 @@ int launch_conv3d_region(int mode, bool out_cf, int in_c4, const float* x, const
     launch_conv_s2_lds(x, in_c4, w, y, B, n, o0, on, pad, bn_scale, bn_shift, bn_mean, s);
     return MVS_OK;
   }
+  // conv_1_0 (S2 32 -> 16) from the fp32 volume, either layout, boxed or whole, any store box: the cell kernel
+  // (bit-equal to the per-lane kernel); the per-lane kernel with per_lane, with bound words (the slot a maximum
+  // lands in follows its wave numbering), for the bf16 / split volumes and for every other shape
+  if (mode == kS2 && s2_cells_shape(CI, CO) && (in_c4 == 0 || in_c4 == 1) && !x2 && !absmax && !y_bound && !per_lane)
+    return launch_s2_cells<32, 16>(x, in_c4, w, y, bn_scale, bn_shift, bn_mean, B, g, s), MVS_OK;
 // two row blocks per wave (one and four measured slower on the cfg-2 eval and train-mode steps)
 #define MVS_REGION_CASE(MD, A, C)                                                       \
   if (mode == MD && CI == A && CO == C) {                                               \
@@ -596,6 +811,16 @@ int launch_conv3d_region(int mode, bool out_cf, int in_c4, const float* x, const
 #undef MVS_REGION_CASE
 #undef MVS_REGION_S2
   return MVS_ERR_INVALID_ARGUMENT;
+}
+
+int conv3d_s2_cells_geometry(int CI, int CO, const int* on, long long* out) {
+  out[0] = kS2CellZ;
+  out[1] = kS2CellY;
+  out[2] = kS2CellRB;
+  out[3] = s2_cell_rows(kS2CellZ, kS2CellY, on);
+  out[4] = s2_cell_waves(kS2CellZ, kS2CellY, kS2CellRB, on);
+  out[5] = s2_cell_grid(kS2CellZ, kS2CellY, kS2CellRB, 1, on).x;
+  return s2_cells_shape(CI, CO) ? 1 : 0;
 }
 
 // Input gradient of the stacked stride-2 convolution (conv_1_0 / conv_2_0 / conv_3_0: 32 -> 112 on the output

@@ -198,6 +198,10 @@ int launch_conv3d_region(int mode, bool out_cf, int in_c4, const float* x, const
                          hipStream_t s, const uint32_t* absmax = nullptr, uint32_t* y_bound = nullptr,
                          bool per_lane = false, const int* st0 = nullptr, const int* stn = nullptr,
                          bool s2_lds = false);
+// the S2 cell kernel's launch for the output region `on`: out = {cell z, cell y, row blocks per wave, GEMM rows,
+// waves, workgroups per sample}; 1 when launch_conv3d_region sends (CI, CO) to it (fp32 volume, no bound words,
+// not per_lane), else 0
+int conv3d_s2_cells_geometry(int CI, int CO, const int* on, long long* out);
 // conv_0_0 (+ BN_0 + ReLU, whole volume) and conv_1_0 (+ BN_1 + ReLU, on its region o0 / on, channels-last)
 // from the fp32 channel-quad cost volume, one fused kernel (conv3d_narrow.hip)
 void launch_conv_head_fp32(const float* cv4, int B, int D, int H, int W, const float* w0wz, const float* bn0_sc,

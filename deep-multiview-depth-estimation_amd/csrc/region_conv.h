@@ -50,6 +50,24 @@ inline dim3 cell_grid(int RB, int B, const int* o0, const int* on, const int* pa
   return dim3(xcd_grid((int)((waves + per_block - 1) / per_block)).x, 1u, (unsigned)B);
 }
 
+// the S2 cell kernel: a GEMM row is a cell of CZ x CY outputs in (z, y) at one output x; rows = the flattened
+// (cell-z, cell-y, x) index, 16 consecutive rows an MFMA row block, RB row blocks per wave.  The (c_in, c_out)
+// it is instantiated for, which are the ones launch_conv3d_region sends to it
+constexpr bool s2_cells_shape(int CI, int CO) { return CI == 32 && CO == 16; }
+
+inline long s2_cell_rows(int CZ, int CY, const int* on) {
+  return (long)((on[0] + CZ - 1) / CZ) * ((on[1] + CY - 1) / CY) * on[2];
+}
+
+inline long s2_cell_waves(int CZ, int CY, int RB, const int* on) {
+  return (s2_cell_rows(CZ, CY, on) + 16 * RB - 1) / (16 * RB);
+}
+
+inline dim3 s2_cell_grid(int CZ, int CY, int RB, int B, const int* on) {
+  const long per_block = kBlock / 64;
+  return dim3(xcd_grid((int)((s2_cell_waves(CZ, CY, RB, on) + per_block - 1) / per_block)).x, 1u, (unsigned)B);
+}
+
 // the LDS-staged kernels: tiles x batch
 inline dim3 tile_grid(int tiles, int B) { return dim3(xcd_grid(tiles).x, (unsigned)B); }
 

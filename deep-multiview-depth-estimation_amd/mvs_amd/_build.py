@@ -25,6 +25,7 @@ HEADERS = [os.path.join(REPO_ROOT, "include", "mvs_cost_volume.h"),
            os.path.join(REPO_ROOT, "include", "train", "mvs_region_train.h"),
            os.path.join(REPO_ROOT, "include", "train", "mvs_loss.h"),
            os.path.join(REPO_ROOT, "include", "fusion", "mvs_depth_filter.h"),
+           os.path.join(REPO_ROOT, "include", "eval", "mvs_region_launch.h"),
            os.path.join(CSRC, "common.h"), os.path.join(CSRC, "launchers.h"),
            os.path.join(CSRC, "packed.h"), os.path.join(CSRC, "region_conv.h"),
            os.path.join(CSRC, "sampling_matrix.h"), os.path.join(CSRC, "split.h"),

@@ -154,6 +154,12 @@ FILTER_SIGNATURES = {
 }
 
 
+# launch geometry of the eval path's region kernels (include/eval/mvs_region_launch.h): host-only, additive
+LAUNCH_SIGNATURES = {
+    "mvs_conv3d_s2_cells_geometry": (_c_int, [_c_int, _c_int, _p, _p]),
+}
+
+
 class MVSLibraryError(RuntimeError):
     """The HIP library is missing, stale, or a kernel call failed."""
 
@@ -171,7 +177,7 @@ def load():
             "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950); there is no CPU fallback" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for table in (SIGNATURES, TRAIN_SIGNATURES, LOSS_SIGNATURES, FILTER_SIGNATURES):
+    for table in (SIGNATURES, TRAIN_SIGNATURES, LOSS_SIGNATURES, FILTER_SIGNATURES, LAUNCH_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)
             fn.restype = res
