@@ -10,6 +10,7 @@
 
 #include "../../include/eval/mvs_region_launch.h"
 #include "../../include/fusion/mvs_depth_filter.h"
+#include "../../include/fusion/mvs_view_fusion.h"
 #include "../../include/train/mvs_loss.h"
 #include "../../include/train/mvs_region_train.h"
 #include "launchers.h"
@@ -1331,6 +1332,31 @@ int mvs_backproject_fwd(const float* depth, const float* K, const float* R, cons
   if (st != MVS_OK) return st;
   const mvs::LaunchCheck lc;
   mvs::launch_backproject(depth, K, R, T, n_views, h, w, xyz, (hipStream_t)stream);
+  return lc.status();
+}
+
+// ---- the fused point cloud (depth_fuse.hip; include/fusion/mvs_view_fusion.h) ----
+size_t mvs_fuse_views_workspace_bytes(int n_views, int h, int w) {
+  if (filter_maps_geometry(n_views, h, w) != MVS_OK) return 0;
+  return (size_t)n_views * (size_t)h * (size_t)w;
+}
+
+int mvs_fuse_views_fwd(const float* depth, const unsigned char* mask, const float* colors, const float* K,
+                       const float* R, const float* T, const int* pairs, const double* matrices, int n_views,
+                       int n_slots, int h, int w, double px_thresh, double rel_thresh, unsigned char* used,
+                       unsigned char* emitted, int* n_merged, float* xyz, float* rgb, void* stream) {
+  if (!aligned4({depth, K, R, T, pairs, n_merged, xyz}) || !matrices || ((uintptr_t)matrices & 7u) || !mask ||
+      !used || !emitted)
+    return MVS_ERR_INVALID_ARGUMENT;
+  if ((colors == nullptr) != (rgb == nullptr) || (colors && !aligned4({colors, rgb}))) return MVS_ERR_INVALID_ARGUMENT;
+  if (!(px_thresh > 0.0 && std::isfinite(px_thresh) && rel_thresh > 0.0 && std::isfinite(rel_thresh)))
+    return MVS_ERR_INVALID_ARGUMENT;
+  int st = filter_pairs_geometry(n_views, n_slots);
+  if (st == MVS_OK) st = filter_maps_geometry(n_views, h, w);
+  if (st != MVS_OK) return st;
+  const mvs::LaunchCheck lc;
+  mvs::launch_fuse_views(depth, mask, colors, K, R, T, pairs, matrices, n_views, n_slots, h, w, px_thresh,
+                         rel_thresh, used, emitted, n_merged, xyz, rgb, (hipStream_t)stream);
   return lc.status();
 }
 

@@ -276,6 +276,14 @@ void launch_geometric_consistency(const float* depth, const int* pairs, const do
 void launch_backproject(const float* depth, const float* K, const float* R, const float* T, int N, int h, int w,
                         float* xyz, hipStream_t s);
 
+// depth_fuse.hip: the fused point cloud (mvs_fuse_views_fwd).  `used` [N][h][w] bytes is zeroed on `s`, then one launch
+// per view in index order; mask, emitted [N][h][w] bytes, merged int32, xyz and rgb [N][h][w][3] (colors and rgb both
+// null or both given)
+void launch_fuse_views(const float* depth, const uint8_t* mask, const float* colors, const float* K, const float* R,
+                       const float* T, const int* pairs, const double* mats, int N, int S, int h, int w,
+                       double px_thresh, double rel_thresh, uint8_t* used, uint8_t* emitted, int* merged, float* xyz,
+                       float* rgb, hipStream_t s);
+
 // dtu_input.hip: data.py:206-210 image normalisation (uint8 HWC -> fp32 NCHW), data.py:300-301
 // depth thresholds
 void launch_normalize_images(const uint8_t* rgb, int n, uint32_t hw, const float* mean3,

@@ -1,6 +1,6 @@
 """ctypes binding of the C ABI in ``include/mvs_cost_volume.h`` and of its training extension
 ``include/train/mvs_region_train.h`` and ``include/train/mvs_loss.h``, and of the depth-map filtering entry points
-in ``include/fusion/mvs_depth_filter.h`` (libmvs_cost_volume.so).
+in ``include/fusion/mvs_depth_filter.h`` and ``include/fusion/mvs_view_fusion.h`` (libmvs_cost_volume.so).
 
 The library is built in-tree by ``mvs_amd._build.build_library()`` (called from
 ``__graft_entry__.build()``) and travels to the GPU box as a file next to this module.  There is
@@ -153,6 +153,13 @@ FILTER_SIGNATURES = {
     "mvs_backproject_fwd": (_c_int, [_p] * 4 + [_c_int] * 3 + [_p, _p]),
 }
 
+# the fused point cloud (include/fusion/mvs_view_fusion.h): additive, under mvs_abi_version; a table of its own, name
+# for name with its header (FILTER_SIGNATURES is mvs_depth_filter.h's)
+FUSE_SIGNATURES = {
+    "mvs_fuse_views_workspace_bytes": (ctypes.c_size_t, [_c_int] * 3),
+    "mvs_fuse_views_fwd": (_c_int, [_p] * 8 + [_c_int] * 4 + [_c_double, _c_double] + [_p] * 6),
+}
+
 
 # launch geometry of the eval path's region kernels (include/eval/mvs_region_launch.h): host-only, additive
 LAUNCH_SIGNATURES = {
@@ -177,7 +184,8 @@ def load():
             "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950); there is no CPU fallback" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for table in (SIGNATURES, TRAIN_SIGNATURES, LOSS_SIGNATURES, FILTER_SIGNATURES, LAUNCH_SIGNATURES):
+    for table in (SIGNATURES, TRAIN_SIGNATURES, LOSS_SIGNATURES, FILTER_SIGNATURES, FUSE_SIGNATURES,
+                  LAUNCH_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)
             fn.restype = res

@@ -8,10 +8,13 @@ reference stops at the depth maps; this is new ground with an API of its own, in
       (within px_thresh pixels and rel_thresh of the depth), and the average of the agreeing depths
   filter_depth(depth, confidence, K, R, T, pairs, ...) -> (mask, depth_avg)
   point_cloud(depth, mask, K, R, T, colors=None) -> points [M, 3] (, colors [M, 3])
+  fused_point_cloud(depth, mask, K, R, T, pairs, colors=None, ...) -> points [M, 3] (, colors [M, 3]) (, n_merged [M])
+      the cloud with each surface point emitted once across the views: views go in index order, a kept pixel that
+      no earlier view has absorbed is emitted and absorbs the pixels of its sources that agree with it
   write_ply(path, points, colors=None)
 
-Everything per pixel runs on the HIP kernels of csrc/depth_filter.hip (include/fusion/mvs_depth_filter.h; DESIGN.md
-§3.10): one thread per output pixel, the geometry in float64, every output written once, no atomics and no host
+Everything per pixel runs on the HIP kernels of csrc/depth_filter.hip and csrc/depth_fuse.hip
+(include/fusion/mvs_depth_filter.h, mvs_view_fusion.h): one thread per output pixel, the geometry in float64, every output written once, no atomics and no host
 synchronisation -- instead of a device-to-host copy per view and a numpy loop over the pairs.  Device tensors only:
 there is no CPU fallback.  Calling these functions is the opt-in: no environment switch selects them, MVSNet.forward
 does not route to them (MVSNet.forward_with_confidence does, for the confidence).
@@ -24,9 +27,12 @@ registers autograd, and the functions above hand them detached tensors, so their
   mvs_fusion::photometric_confidence(prob_volume, depth, d_batch) -> conf
   mvs_fusion::view_pair_matrices(K, R, T, pairs) -> matrices [N, S, 24] float64
   mvs_fusion::geometric_consistency(depth, pairs, matrices, px_thresh, rel_thresh) -> (n_consistent, depth_avg)
-  mvs_fusion::backproject(depth, K, R, T) -> xyz [N, h, w, 3]"""
+  mvs_fusion::backproject(depth, K, R, T) -> xyz [N, h, w, 3]
+  mvs_fusion::fuse_views(depth, mask, colors?, K, R, T, pairs, matrices, px_thresh, rel_thresh)
+      -> (emitted bool [N, h, w], n_merged int32 [N, h, w], xyz [N, h, w, 3], rgb [N, h, w, 3] or empty)"""
+import ctypes
 import math
-from typing import Tuple
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
@@ -268,7 +274,7 @@ def point_cloud(depth, mask, K, R, T, colors=None):
     the same order.  One kernel over all pixels, then one boolean index.
 
     There is no cross-view de-duplication: each view contributes its own surviving pixels, so a surface point seen
-    consistently by several views appears once per view."""
+    consistently by several views appears once per view; fused_point_cloud emits it once."""
     xyz = backproject(depth, K, R, T)
     if mask.shape != depth.shape or mask.dtype != torch.bool:
         raise ValueError("mask must be bool %s, got %s %s" % (tuple(depth.shape), mask.dtype, tuple(mask.shape)))
@@ -280,6 +286,102 @@ def point_cloud(depth, mask, K, R, T, colors=None):
         raise ValueError("colors must be [N, C, h, w] over the depth maps %s, got %s"
                          % (tuple(depth.shape), tuple(colors.shape)))
     return points, colors.to(xyz.device).permute(0, 2, 3, 1)[keep]
+
+
+# ----------------------------------------------------------------------------------------------
+# mvs_fusion::fuse_views
+# ----------------------------------------------------------------------------------------------
+@torch.library.custom_op("mvs_fusion::fuse_views", mutates_args=())
+def fuse_views_op(depth: torch.Tensor, mask: torch.Tensor, colors: Optional[torch.Tensor], K: torch.Tensor,
+                  R: torch.Tensor, T: torch.Tensor, pairs: torch.Tensor, matrices: torch.Tensor, px_thresh: float,
+                  rel_thresh: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(emitted bool [N, h, w], n_merged int32 [N, h, w], xyz fp32 [N, h, w, 3], rgb fp32 [N, h, w, 3] or an empty
+    tensor without colors) of depth fp32 [N, 1, h, w], mask bool or uint8 [N, 1, h, w] (non-zero keeps), colors fp32
+    [N, 3, h, w] or None, the cameras, pairs int32 [N, S] and the matrices view_pair_matrices formed for them, all
+    on one device.  Views go in index order, one launch each on the current stream; the workspace is allocated and
+    zeroed by the call.  (mvs_fuse_views_fwd)"""
+    depth = _depth_maps(depth, "fuse_views")
+    lib = _lib.load()
+    n, _, h, w = depth.shape
+    dev = depth.device
+    if tuple(mask.shape) != (n, 1, h, w) or mask.dtype not in (torch.bool, torch.uint8) or mask.device != dev:
+        raise ValueError("mask must be bool or uint8 %s on the depth maps' device, got %s %s on %s"
+                         % ((n, 1, h, w), mask.dtype, tuple(mask.shape), mask.device))
+    if colors is not None and (tuple(colors.shape) != (n, 3, h, w) or colors.dtype != _F32 or colors.device != dev):
+        raise ValueError("colors must be fp32 %s on the depth maps' device, got %s %s on %s"
+                         % ((n, 3, h, w), colors.dtype, tuple(colors.shape), colors.device))
+    if pairs.dim() != 2 or pairs.dtype != torch.int32 or pairs.device != dev or pairs.shape[0] != n:
+        raise ValueError("pairs must be int32 [%d, S] on the depth maps' device, got %s %s on %s"
+                         % (n, pairs.dtype, tuple(pairs.shape), pairs.device))
+    s = pairs.shape[1]
+    if tuple(matrices.shape) != (n, s, 24) or matrices.dtype != torch.float64 or matrices.device != dev:
+        raise ValueError("matrices must be float64 [%d, %d, 24] on the depth maps' device, got %s %s on %s"
+                         % (n, s, matrices.dtype, tuple(matrices.shape), matrices.device))
+    for v, name in ((px_thresh, "px_thresh"), (rel_thresh, "rel_thresh")):
+        if not (math.isfinite(v) and v > 0.0):
+            raise ValueError("fuse_views: %s must be finite and > 0, got %r" % (name, v))
+    K, R, T = _view_cams(K, R, T, dev, n, "fuse_views")
+    mask, pairs, matrices = mask.contiguous(), pairs.contiguous(), matrices.contiguous()
+    colors = None if colors is None else colors.contiguous()
+    used = torch.empty((lib.mvs_fuse_views_workspace_bytes(n, h, w),), device=dev, dtype=torch.uint8)
+    emitted = torch.empty((n, h, w), device=dev, dtype=torch.bool)
+    merged = torch.empty((n, h, w), device=dev, dtype=torch.int32)
+    xyz = torch.empty((n, h, w, 3), device=dev, dtype=_F32)
+    rgb = torch.empty((n, h, w, 3) if colors is not None else (0,), device=dev, dtype=_F32)
+    null = ctypes.c_void_p(0)
+    st = lib.mvs_fuse_views_fwd(_lib.ptr(depth), _lib.ptr(mask), null if colors is None else _lib.ptr(colors),
+                                _lib.ptr(K), _lib.ptr(R), _lib.ptr(T), _lib.ptr(pairs), _lib.ptr(matrices), n, s, h, w,
+                                float(px_thresh), float(rel_thresh), _lib.ptr(used), _lib.ptr(emitted),
+                                _lib.ptr(merged), _lib.ptr(xyz), null if colors is None else _lib.ptr(rgb),
+                                _lib.stream_handle(dev))
+    _lib.check(st, "mvs_fuse_views_fwd")
+    return emitted, merged, xyz, rgb
+
+
+@fuse_views_op.register_fake
+def _(depth, mask, colors, K, R, T, pairs, matrices, px_thresh, rel_thresh):
+    n, _, h, w = depth.shape
+    return (depth.new_empty((n, h, w), dtype=torch.bool), depth.new_empty((n, h, w), dtype=torch.int32),
+            depth.new_empty((n, h, w, 3), dtype=_F32),
+            depth.new_empty((n, h, w, 3) if colors is not None else (0,), dtype=_F32))
+
+
+def fused_point_cloud(depth, mask, K, R, T, pairs, colors=None, px_thresh=1.0, rel_thresh=0.01, return_counts=False):
+    """points [M, 3] fp32 in world coordinates with each surface point emitted once across the views of a scan, in
+    view, row, column order like point_cloud; with colors fp32 [N, 3, h, w] also their colours [M, 3] fp32, and with
+    return_counts also n_merged int32 [M] (the order of the result: points, colors, n_merged).
+
+    depth [N, 1, h, w] fp32 on the device and mask bool [N, 1, h, w] (what filter_depth returns: its depth_avg or
+    the raw maps, and its mask); the cameras and ``pairs`` as geometric_consistency takes them.  Views go in index
+    order (permute the inputs for another order).  A pixel of view n is emitted when the mask keeps it, its depth
+    is > 0 and no earlier view has absorbed it.  It merges every source that agrees with it after
+    geometric_consistency's round trip (same px_thresh / rel_thresh gates, in float64) and absorbs the source pixel
+    nearest to where it lands there, which that view then does not emit.  Its point is the back-projection of
+    (d + the sum of the merged d_r) / (1 + n_merged), its colour the mean of its own and the merged sources'
+    bilinear colours.  A source pixel that an earlier view has absorbed may still contribute to an average: the
+    result does not depend on the order in which the pixels of one view run.  One launch per view, one boolean
+    index; not differentiable."""
+    n = depth.shape[0] if isinstance(depth, torch.Tensor) and depth.dim() else 0
+    table = pair_table(pairs, n)
+    depth = _depth_maps(depth.detach(), "fused_point_cloud")
+    if mask.shape != depth.shape or mask.dtype != torch.bool:
+        raise ValueError("mask must be bool %s, got %s %s" % (tuple(depth.shape), mask.dtype, tuple(mask.shape)))
+    if colors is not None:
+        if colors.dim() != 4 or colors.shape[0] != n or colors.shape[1] != 3 or colors.shape[2:] != depth.shape[2:]:
+            raise ValueError("colors must be [N, 3, h, w] over the depth maps %s, got %s"
+                             % (tuple(depth.shape), tuple(colors.shape)))
+        colors = colors.detach().to(device=depth.device, dtype=_F32)
+    K, R, T = _view_cams(K.detach(), R.detach(), T.detach(), depth.device, n, "fused_point_cloud")
+    table = table.to(depth.device)
+    matrices = view_pair_matrices(K, R, T, table)
+    emitted, merged, xyz, rgb = fuse_views_op(depth, mask.detach().to(depth.device), colors, K, R, T, table, matrices,
+                                              float(px_thresh), float(rel_thresh))
+    out = [xyz[emitted]]
+    if colors is not None:
+        out.append(rgb[emitted])
+    if return_counts:
+        out.append(merged[emitted])
+    return out[0] if len(out) == 1 else tuple(out)
 
 
 def write_ply(path, points, colors=None):

@@ -11,6 +11,8 @@
  *
  * Cameras: K, R [n][3][3], T [n][3] fp32 with x_cam = R x_world + T, K for the map's own resolution, pixel (x, y) =
  * integer column and row indices.  A depth is valid when it is > 0 (0, negative and NaN are not).
+ *
+ * The last stage, the cloud with each surface point emitted once across the views, is mvs_view_fusion.h.
  */
 #ifndef MVS_DEPTH_FILTER_H
 #define MVS_DEPTH_FILTER_H

@@ -7,7 +7,10 @@ Two sizes: a DTU scan (N = 49 views, S = 10 sources, 128 x 160 maps; the confide
 map size (N = 5, S = 4, 296 x 400; D = 48).  Per size and kernel: a warm-up, then ``rounds`` alternations of (kernel x
 iters, torch expression x max(1, iters / 10)), each timed with one event pair around the loop; the median per-call
 time over the rounds and the min .. max spread are printed.  The torch expression follows the same definitions
-(include/fusion/mvs_depth_filter.h) in float64 tensor ops, the pairs in a Python loop as a user would write it."""
+(include/fusion/mvs_depth_filter.h) in float64 tensor ops, the pairs in a Python loop as a user would write it.
+The fused cloud (include/fusion/mvs_view_fusion.h) follows: fusion.fused_point_cloud beside its rule in torch, then
+the fuse_views op beside the unfused route (consistency + point_cloud) and beside its own N launches over an
+all-false mask (what the launches alone cost)."""
 import argparse
 import os
 import sys
@@ -108,6 +111,56 @@ def torch_backproject(depth, K, R, T):
     return xyz.reshape(N, h, w, 3).to(torch.float32)
 
 
+def torch_fused_cloud(depth, mask, K, R, T, mats, table, px, rel):
+    """points [M, 3] as fusion.fused_point_cloud without colours (mvs_fuse_views_fwd's rule), float64 tensor ops, a
+    Python loop over views and slots, the ``used`` flags carried from view to view."""
+    N, _, h, w = depth.shape
+    ys, xs = torch.meshgrid(torch.arange(h, device=depth.device, dtype=F64),
+                            torch.arange(w, device=depth.device, dtype=F64), indexing="ij")
+    pix = torch.stack([xs, ys, torch.ones_like(xs)], -1)
+    tab = table.cpu().tolist()
+    used = torch.zeros((N, h, w), dtype=torch.bool, device=depth.device)
+    Kinv, Rd, Td = torch.linalg.inv(K.to(F64)), R.to(F64), T.to(F64).reshape(N, 3)
+    points = []
+    for n in range(N):
+        d = depth[n, 0].to(F64)
+        em = mask[n, 0] & (d > 0) & ~used[n]
+        total = torch.zeros_like(d)
+        cnt = torch.zeros_like(d)
+        for s, src in enumerate(tab[n]):
+            if src < 0 or src >= N or src == n:
+                continue
+            M = mats[n, s]
+            pz = d * (M[6] * xs + M[7] * ys + M[8]) + M[11]
+            alive = em & (pz > 0)
+            x = (d * (M[0] * xs + M[1] * ys + M[2]) + M[9]) / pz
+            y = (d * (M[3] * xs + M[4] * ys + M[5]) + M[10]) / pz
+            x0, y0 = torch.floor(x), torch.floor(y)
+            alive = alive & (x0 >= 0) & (x0 <= w - 2) & (y0 >= 0) & (y0 <= h - 2)
+            ix = torch.where(alive, x0, torch.zeros_like(x0)).long()
+            iy = torch.where(alive, y0, torch.zeros_like(y0)).long()
+            S = depth[src, 0]
+            ix1, iy1 = (ix + 1).clamp(max=w - 1), (iy + 1).clamp(max=h - 1)
+            t00, t01, t10, t11 = S[iy, ix], S[iy, ix1], S[iy1, ix], S[iy1, ix1]
+            alive = alive & (t00 > 0) & (t01 > 0) & (t10 > 0) & (t11 > 0)
+            fx, fy = x - x0, y - y0
+            ds = (1 - fy) * ((1 - fx) * t00.to(F64) + fx * t01.to(F64)) + fy * ((1 - fx) * t10.to(F64) + fx * t11.to(F64))
+            qz = ds * (M[18] * x + M[19] * y + M[20]) + M[23]
+            alive = alive & (qz > 0)
+            xr = (ds * (M[12] * x + M[13] * y + M[14]) + M[21]) / qz
+            yr = (ds * (M[15] * x + M[16] * y + M[17]) + M[22]) / qz
+            ok = alive & ((xr - xs) ** 2 + (yr - ys) ** 2 < px * px) & ((qz - d).abs() < rel * d)
+            xn = torch.where(ok, torch.floor(x + 0.5), torch.zeros_like(x)).clamp(0, w - 1).long()
+            yn = torch.where(ok, torch.floor(y + 0.5), torch.zeros_like(y)).clamp(0, h - 1).long()
+            used[src].index_put_((yn[ok], xn[ok]), torch.ones((), dtype=torch.bool, device=depth.device))
+            total = total + torch.where(ok, qz, torch.zeros_like(qz))
+            cnt = cnt + ok.to(F64)
+        dm = (d + total) / (1 + cnt)
+        cam = dm.unsqueeze(-1) * (pix @ Kinv[n].transpose(-1, -2)) - Td[n]
+        points.append((cam @ Rd[n])[em].to(torch.float32))
+    return torch.cat(points)
+
+
 def timed(fn, iters):
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record()
@@ -118,7 +171,7 @@ def timed(fn, iters):
     return a.elapsed_time(b) / iters * 1e3          # microseconds per call
 
 
-def ab(name, kernel, expression, rounds, iters, emit):
+def ab(name, kernel, expression, rounds, iters, emit, other="torch float64"):
     slow = max(1, iters // 10)
     timed(kernel, 10)
     timed(expression, 2)
@@ -126,8 +179,8 @@ def ab(name, kernel, expression, rounds, iters, emit):
     for _ in range(rounds):
         k.append(timed(kernel, iters))
         e.append(timed(expression, slow))
-    emit("  %-24s kernel %9.1f us (%.1f .. %.1f)   torch float64 %11.1f us (%.1f .. %.1f)   x%.0f"
-         % (name, np.median(k), min(k), max(k), np.median(e), min(e), max(e), np.median(e) / np.median(k)))
+    emit("  %-24s kernel %9.1f us (%.1f .. %.1f)   %s %11.1f us (%.1f .. %.1f)   x%.2g"
+         % (name, np.median(k), min(k), max(k), other, np.median(e), min(e), max(e), np.median(e) / np.median(k)))
 
 
 def main():
@@ -171,6 +224,29 @@ def main():
            lambda: torch_consistency(depth, mats, table, 1.0, 0.01), args.rounds, args.iters, emit)
         ab("back-projection", lambda: fusion.backproject_op(depth, K, R, T),
            lambda: torch_backproject(depth, K, R, T), args.rounds, args.iters, emit)
+        # the fused cloud: the public call (pair matrices, N launches, one boolean index) beside the same rule in
+        # torch; the unfused route (consistency + point_cloud) beside the N launches over an all-false mask, which
+        # is what the launches alone cost
+        mask = (depth > 0) & (c0 >= 1)
+        none = torch.zeros_like(mask)
+        pairs = table.cpu()
+        pts = fusion.fused_point_cloud(depth, mask, K, R, T, pairs)
+        ref = torch_fused_cloud(depth, mask, K, R, T, mats, table, 1.0, 0.01)
+        assert abs(pts.shape[0] - ref.shape[0]) <= 1e-3 * ref.shape[0]
+        if pts.shape == ref.shape:
+            assert torch.allclose(pts, ref, rtol=1e-6, atol=1e-4)
+        emit("  (fused cloud: %d points of %d kept pixels)" % (pts.shape[0], int(mask.sum())))
+        ab("fused_point_cloud", lambda: fusion.fused_point_cloud(depth, mask, K, R, T, pairs),
+           lambda: torch_fused_cloud(depth, mask, K, R, T, mats, table, 1.0, 0.01), args.rounds, args.iters, emit)
+
+        def unfused():
+            fusion.geometric_consistency_op(depth, table, mats, 1.0, 0.01)
+            return fusion.point_cloud(depth, mask, K, R, T)
+        fuse_op = lambda m: fusion.fuse_views_op(depth, m, None, K, R, T, table, mats, 1.0, 0.01)
+        ab("fuse_views op", lambda: fuse_op(mask), unfused, args.rounds, args.iters, emit,
+           other="consistency + point_cloud")
+        ab("fuse_views op", lambda: fuse_op(mask), lambda: fuse_op(none), args.rounds, args.iters, emit,
+           other="its N launches, empty mask")
     emit("(kernel times include the op call's host side: the loop is launch-bound where a kernel is shorter than it)")
     if args.out:
         with open(args.out, "w") as f:
