@@ -9,6 +9,7 @@
 #include <initializer_list>
 
 #include "../../include/eval/mvs_region_launch.h"
+#include "../../include/fusion/mvs_cloud_eval.h"
 #include "../../include/fusion/mvs_depth_filter.h"
 #include "../../include/fusion/mvs_view_fusion.h"
 #include "../../include/train/mvs_loss.h"
@@ -1357,6 +1358,77 @@ int mvs_fuse_views_fwd(const float* depth, const unsigned char* mask, const floa
   const mvs::LaunchCheck lc;
   mvs::launch_fuse_views(depth, mask, colors, K, R, T, pairs, matrices, n_views, n_slots, h, w, px_thresh,
                          rel_thresh, used, emitted, n_merged, xyz, rgb, (hipStream_t)stream);
+  return lc.status();
+}
+
+}  // extern "C"
+
+// ---- nearest-neighbour distances between two clouds (cloud_nn.hip; include/fusion/mvs_cloud_eval.h) ----
+namespace {
+int cloud_count(long long n) {
+  if (n < 0) return MVS_ERR_INVALID_ARGUMENT;
+  return n >= (1ll << 31) ? MVS_ERR_TOO_LARGE : MVS_OK;
+}
+// MVS_OK for a grid the kernels can index: dimensions >= 1, at most MVS_CLOUD_MAX_CELLS cells
+int cloud_grid_geometry(int nx, int ny, int nz) {
+  if (nx < 1 || ny < 1 || nz < 1) return MVS_ERR_INVALID_ARGUMENT;
+  const uint64_t cells = (uint64_t)nx * (uint64_t)ny * (uint64_t)nz;   // (read only once nx ny < 2^31: no wrap)
+  if ((uint64_t)nx * (uint64_t)ny >= (1ull << 31) || cells >= (1ull << 31)) return MVS_ERR_TOO_LARGE;
+  return cells > (uint64_t)MVS_CLOUD_MAX_CELLS ? MVS_ERR_INVALID_ARGUMENT : MVS_OK;
+}
+int cloud_grid_ok(double ox, double oy, double oz, double cell, int nx, int ny, int nz) {
+  if (!(std::isfinite(ox) && std::isfinite(oy) && std::isfinite(oz) && cell > 0.0 && std::isfinite(cell)))
+    return MVS_ERR_INVALID_ARGUMENT;
+  return cloud_grid_geometry(nx, ny, nz);
+}
+}  // namespace
+
+extern "C" {
+
+size_t mvs_cloud_cell_table_bytes(int nx, int ny, int nz) {
+  if (cloud_grid_geometry(nx, ny, nz) != MVS_OK) return 0;
+  return ((size_t)nx * (size_t)ny * (size_t)nz + 1) * sizeof(int);
+}
+
+int mvs_cloud_cell_keys(const float* points, long long n, double origin_x, double origin_y, double origin_z,
+                        double cell, int nx, int ny, int nz, int* keys, void* stream) {
+  if (!aligned4({points, keys})) return MVS_ERR_INVALID_ARGUMENT;
+  int st = cloud_count(n);
+  if (st == MVS_OK) st = cloud_grid_ok(origin_x, origin_y, origin_z, cell, nx, ny, nz);
+  if (st != MVS_OK || n == 0) return st;
+  const mvs::LaunchCheck lc;
+  mvs::launch_cloud_cell_keys(points, (int)n, origin_x, origin_y, origin_z, cell, nx, ny, nz, keys,
+                              (hipStream_t)stream);
+  return lc.status();
+}
+
+int mvs_cloud_cell_ranges(const int* sorted_keys, long long n, long long ncells, int* cell_start, void* stream) {
+  if (!aligned4({sorted_keys, cell_start})) return MVS_ERR_INVALID_ARGUMENT;
+  int st = cloud_count(n);
+  if (st == MVS_OK) st = cloud_count(ncells);
+  if (st != MVS_OK) return st;
+  if (ncells < 1 || ncells > MVS_CLOUD_MAX_CELLS) return MVS_ERR_INVALID_ARGUMENT;
+  const mvs::LaunchCheck lc;
+  mvs::launch_cloud_cell_ranges(sorted_keys, (int)n, (int)ncells, cell_start, (hipStream_t)stream);
+  return lc.status();
+}
+
+int mvs_cloud_nearest(const float* query, const int* query_order, long long m, const float* targets,
+                      const int* target_index, long long g, const int* cell_start, double origin_x, double origin_y,
+                      double origin_z, double cell, int nx, int ny, int nz, double max_dist, float* dist, int* index,
+                      void* stream) {
+  if (!aligned4({query, query_order, targets, target_index, cell_start, dist, index})) return MVS_ERR_INVALID_ARGUMENT;
+  int st = cloud_count(m);
+  if (st == MVS_OK) st = cloud_count(g);
+  if (st == MVS_OK) st = cloud_grid_ok(origin_x, origin_y, origin_z, cell, nx, ny, nz);
+  if (st != MVS_OK) return st;
+  if (!(max_dist > 0.0 && std::isfinite(max_dist))) return MVS_ERR_INVALID_ARGUMENT;
+  const double rings = std::ceil(max_dist / cell);
+  if (!(rings <= (double)MVS_CLOUD_MAX_RINGS)) return MVS_ERR_INVALID_ARGUMENT;
+  if (m == 0) return MVS_OK;
+  const mvs::LaunchCheck lc;
+  mvs::launch_cloud_nearest(query, query_order, (int)m, targets, target_index, (int)g, cell_start, origin_x, origin_y,
+                            origin_z, cell, nx, ny, nz, (int)rings, max_dist, dist, index, (hipStream_t)stream);
   return lc.status();
 }
 

@@ -284,6 +284,18 @@ void launch_fuse_views(const float* depth, const uint8_t* mask, const float* col
                        double px_thresh, double rel_thresh, uint8_t* used, uint8_t* emitted, int* merged, float* xyz,
                        float* rgb, hipStream_t s);
 
+// cloud_nn.hip: nearest-neighbour distances between two clouds on a uniform grid (include/fusion/mvs_cloud_eval.h).
+// keys [n] = the linear cell of each point (nx ny nz for a non-finite one); cell_start [ncells + 1] from the sorted
+// keys (n == 0: zeros); nearest: query [m][3] and its cell order, targets [n_targets][3] in cell order with their
+// original indices, rings = ceil(max_dist / cell); n_targets == 0 fills dist / index with +inf / -1
+void launch_cloud_cell_keys(const float* points, int n, double ox, double oy, double oz, double cell, int nx, int ny,
+                            int nz, int* keys, hipStream_t s);
+void launch_cloud_cell_ranges(const int* sorted_keys, int n, int ncells, int* cell_start, hipStream_t s);
+void launch_cloud_nearest(const float* query, const int* query_order, int m, const float* targets,
+                          const int* target_index, int n_targets, const int* cell_start, double ox, double oy,
+                          double oz, double cell, int nx, int ny, int nz, int rings, double max_dist, float* dist,
+                          int* index, hipStream_t s);
+
 // dtu_input.hip: data.py:206-210 image normalisation (uint8 HWC -> fp32 NCHW), data.py:300-301
 // depth thresholds
 void launch_normalize_images(const uint8_t* rgb, int n, uint32_t hw, const float* mean3,

@@ -20,12 +20,13 @@ SOURCES = [os.path.join(CSRC, f) for f in ("capi.hip", "plane_sampling.hip", "co
                                            "conv3d_region_wgrad.hip", "conv3d_s2_wgrad.hip",
                                            "conv3d_t2_wgrad.hip", "deconv3d_region_bwd.hip",
                                            "bn_train_bwd.hip", "conv2d_bwd.hip", "loss.hip",
-                                           "depth_filter.hip", "depth_fuse.hip")]
+                                           "depth_filter.hip", "depth_fuse.hip", "cloud_nn.hip")]
 HEADERS = [os.path.join(REPO_ROOT, "include", "mvs_cost_volume.h"),
            os.path.join(REPO_ROOT, "include", "train", "mvs_region_train.h"),
            os.path.join(REPO_ROOT, "include", "train", "mvs_loss.h"),
            os.path.join(REPO_ROOT, "include", "fusion", "mvs_depth_filter.h"),
            os.path.join(REPO_ROOT, "include", "fusion", "mvs_view_fusion.h"),
+           os.path.join(REPO_ROOT, "include", "fusion", "mvs_cloud_eval.h"),
            os.path.join(REPO_ROOT, "include", "eval", "mvs_region_launch.h"),
            os.path.join(CSRC, "common.h"), os.path.join(CSRC, "launchers.h"),
            os.path.join(CSRC, "packed.h"), os.path.join(CSRC, "region_conv.h"),

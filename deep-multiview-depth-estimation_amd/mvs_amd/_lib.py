@@ -1,6 +1,7 @@
 """ctypes binding of the C ABI in ``include/mvs_cost_volume.h`` and of its training extension
 ``include/train/mvs_region_train.h`` and ``include/train/mvs_loss.h``, and of the depth-map filtering entry points
-in ``include/fusion/mvs_depth_filter.h`` and ``include/fusion/mvs_view_fusion.h`` (libmvs_cost_volume.so).
+in ``include/fusion/mvs_depth_filter.h``, ``include/fusion/mvs_view_fusion.h`` and
+``include/fusion/mvs_cloud_eval.h`` (libmvs_cost_volume.so).
 
 The library is built in-tree by ``mvs_amd._build.build_library()`` (called from
 ``__graft_entry__.build()``) and travels to the GPU box as a file next to this module.  There is
@@ -160,6 +161,18 @@ FUSE_SIGNATURES = {
     "mvs_fuse_views_fwd": (_c_int, [_p] * 8 + [_c_int] * 4 + [_c_double, _c_double] + [_p] * 6),
 }
 
+# nearest-neighbour distances between two clouds (include/fusion/mvs_cloud_eval.h): additive, under mvs_abi_version;
+# counts are long long so that one past the index width is refused, not truncated
+CLOUD_MAX_CELLS, CLOUD_MAX_RINGS = 1 << 27, 64
+_c_ll = ctypes.c_longlong
+_CLOUD_GRID = [_c_double] * 4 + [_c_int] * 3            # origin x, y, z, cell, nx, ny, nz
+CLOUD_SIGNATURES = {
+    "mvs_cloud_cell_table_bytes": (ctypes.c_size_t, [_c_int] * 3),
+    "mvs_cloud_cell_keys": (_c_int, [_p, _c_ll] + _CLOUD_GRID + [_p, _p]),
+    "mvs_cloud_cell_ranges": (_c_int, [_p, _c_ll, _c_ll, _p, _p]),
+    "mvs_cloud_nearest": (_c_int, [_p, _p, _c_ll, _p, _p, _c_ll, _p] + _CLOUD_GRID + [_c_double, _p, _p, _p]),
+}
+
 
 # launch geometry of the eval path's region kernels (include/eval/mvs_region_launch.h): host-only, additive
 LAUNCH_SIGNATURES = {
@@ -185,7 +198,7 @@ def load():
             "(hipcc --offload-arch=gfx950); there is no CPU fallback" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
     for table in (SIGNATURES, TRAIN_SIGNATURES, LOSS_SIGNATURES, FILTER_SIGNATURES, FUSE_SIGNATURES,
-                  LAUNCH_SIGNATURES):
+                  CLOUD_SIGNATURES, LAUNCH_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)
             fn.restype = res

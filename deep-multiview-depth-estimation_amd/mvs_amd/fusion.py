@@ -12,6 +12,7 @@ reference stops at the depth maps; this is new ground with an API of its own, in
       the cloud with each surface point emitted once across the views: views go in index order, a kept pixel that
       no earlier view has absorbed is emitted and absorbs the pixels of its sources that agree with it
   write_ply(path, points, colors=None)
+  read_ply(path) -> (points, colors or None)
 
 Everything per pixel runs on the HIP kernels of csrc/depth_filter.hip and csrc/depth_fuse.hip
 (include/fusion/mvs_depth_filter.h, mvs_view_fusion.h): one thread per output pixel, the geometry in float64, every output written once, no atomics and no host
@@ -412,3 +413,64 @@ def write_ply(path, points, colors=None):
     with open(path, "wb") as f:
         f.write(("\n".join(header + ["end_header"]) + "\n").encode("ascii"))
         f.write(rec.tobytes())
+
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2",
+              "ushort": "u2", "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4",
+              "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def read_ply(path):
+    """(points float32 [M, 3], colors uint8 [M, 3] or None) of a PLY file, what write_ply writes and what ground-truth
+    clouds come as: ``binary_little_endian`` or ``ascii``, ``vertex`` the first element, scalar vertex properties of
+    any PLY type; x, y, z are read from float or double, red, green, blue when all three are there, other vertex
+    properties are skipped and later elements (faces) ignored.  ValueError for a list property inside ``vertex``, a
+    big-endian file and a body shorter than its header says.  Numpy only."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header")
+    if not data.startswith(b"ply") or end < 0:
+        raise ValueError("%s: not a PLY file" % path)
+    body = data.find(b"\n", end) + 1
+    lines = [ln.split() for ln in data[:end].decode("ascii", "replace").splitlines()[1:]]
+    lines = [ln for ln in lines if ln and ln[0] not in ("comment", "obj_info")]
+    if not lines or lines[0][0] != "format" or len(lines[0]) < 2:
+        raise ValueError("%s: no format line" % path)
+    fmt = lines[0][1]
+    if fmt not in ("binary_little_endian", "ascii"):
+        raise ValueError("%s: format %s is not supported (binary_little_endian and ascii are)" % (path, fmt))
+    if len(lines) < 2 or lines[1][:2] != ["element", "vertex"] or len(lines[1]) != 3:
+        raise ValueError("%s: vertex must be the first element" % path)
+    count, fields = int(lines[1][2]), []
+    for ln in lines[2:]:
+        if ln[0] == "element":
+            break
+        if ln[0] != "property":
+            raise ValueError("%s: unexpected header line %r" % (path, " ".join(ln)))
+        if ln[1] == "list":
+            raise ValueError("%s: a list property inside vertex is not supported" % path)
+        if len(ln) != 3 or ln[1] not in _PLY_TYPES:
+            raise ValueError("%s: unknown property %r" % (path, " ".join(ln)))
+        fields.append((ln[2], "<" + _PLY_TYPES[ln[1]]))
+    names = [n for n, _ in fields]
+    if len(set(names)) != len(names) or not all(k in names for k in "xyz"):
+        raise ValueError("%s: vertex needs properties x, y and z, each once" % path)
+    if any(dict(fields)[k] not in ("<f4", "<f8") for k in "xyz"):
+        raise ValueError("%s: x, y, z must be float or double" % path)
+    dtype = np.dtype(fields)
+    if fmt == "ascii":
+        tokens = data[body:].split()
+        if len(tokens) < count * len(fields):
+            raise ValueError("%s: the body ends before %d vertices" % (path, count))
+        table = np.array(tokens[:count * len(fields)], dtype="S").reshape(count, len(fields))
+        rec = np.empty(count, dtype=dtype)
+        for k, (name, kind) in enumerate(fields):
+            rec[name] = table[:, k].astype(np.float64).astype(kind)
+    else:
+        if len(data) - body < count * dtype.itemsize:
+            raise ValueError("%s: the body ends before %d vertices" % (path, count))
+        rec = np.frombuffer(data, dtype=dtype, count=count, offset=body)
+    points = np.stack([rec[k].astype(np.float32) for k in "xyz"], 1).reshape(count, 3)
+    if not all(k in names for k in ("red", "green", "blue")):
+        return points, None
+    return points, np.stack([rec[k].astype(np.uint8) for k in ("red", "green", "blue")], 1).reshape(count, 3)
